@@ -6,7 +6,12 @@
 A "step" is one full training iteration of DEAL-YOLO-N (yolov8n-ASF-P2P2) at 640x640, per-GPU batch 64 (BASELINE.json
 configs[1]): image import, forward, detection loss (TAL + CIoU + DFL + BCE), hand-written backward, gradient all-reduce
 (RCCL, N>1), SGD-nesterov + EMA -- all through libdealyolo_hip.so.  Inputs are synthetic and already resident in HBM.
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline; what else the line
+can hold is measured only with --full (without it: null), and --no-cpu / --probe 0 / --secondary 0 leave parts of --full out.
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32: loss_items (box, cls, dfl),
+loss, and the model's parameters, their gradients, the EMA parameters and the BatchNorm running statistics, each flattened
+in model.named_parameters() / buffers() order.  Measured with --full:
+  config.device_ms_by_call  device ms per C-ABI function, from the roofline probe's event-timed replay of the launch list;
   roofline     SURVEY.md 8(d) throughout: `achieved` / `frac` = ALGORITHMIC bytes per launch / average launch duration of the dominant
                kernel -- the kernel group with the largest total time per step among the launches that have algorithmic bytes
                (convolutions: forward, input gradient, weight gradient, stem) -- measured live with HIP events on the launch stream,
@@ -19,8 +24,8 @@ Prints ONE JSON line on rank 0.  Extra objects:
                8(d) step fraction;
   cpu_baseline the CPU oracle (a port of the reference's PyTorch CPU path) timed on the host cores in BASELINE.md section 2's protocol
                (bs=2, median of 8 steps after 2 warm-up); `bs16` = the same at bs=16 (about 25 s of CPU work: the bounded sample).
---loss ciou|wiou|ciou+nwd|wiou+nwd selects the box loss: the default is the north-star's wiou+nwd; the reference-default ciou rate is
-measured beside it (config.ciou_images_per_s: the same launch list replayed eagerly with the other loss mode).
+--loss ciou|wiou|ciou+nwd|wiou+nwd selects the box loss: the default is the north-star's wiou+nwd; with --full the reference-default
+ciou rate is measured beside it (config.ciou_images_per_s: the same launch list replayed eagerly with the other loss mode).
 --gpus N from a plain `python bench.py` start re-launches itself under torch.distributed.run (one rank per GPU) as a CHILD process
 before anything touches the GPU, like YOLO.train(device='0,1,..') does (reference engine/trainer.py:607-627, utils/dist.py:47-65).
 """
@@ -171,6 +176,22 @@ def cpu_baseline(imgsz):
             "bs16": v16}
 
 
+def dump_outputs(out_dir, plan, model):
+    """--dump-outputs: what the last step handed its caller, as float32 .npy files (about 16 MB for DEAL-YOLO-N)."""
+    os.makedirs(out_dir, exist_ok=True)
+    rt = plan.rt
+    spans = [(rt.param_off[n], p.numel()) for n, p in model.named_parameters()]
+
+    def flat(buf):
+        return torch.cat([buf[o:o + k] for o, k in spans]).float().cpu().numpy()
+
+    loss, items = plan.loss_items()
+    out = {"loss_items": items.float().numpy(), "loss": np.array([loss], np.float32), "params": flat(rt.flat_p), "grads": flat(rt.flat_g),
+           "ema": flat(plan.ema), "bn_stats": torch.cat([b.reshape(-1) for b in model.buffers() if b.dtype.is_floating_point]).float().cpu().numpy()}
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def relaunch(a):
     """--gpus N without a launcher: start `python -m torch.distributed.run --nproc-per-node N bench.py <same arguments>` as a child
     process -- nothing in this process has touched the GPU yet -- and relay its output (rank 0 prints the JSON line)."""
@@ -204,6 +225,9 @@ def main():
                     "tiny test configurations pass a smaller one so that no step overflows)")
     ap.add_argument("--loss", default="wiou+nwd", choices=["ciou", "wiou", "ciou+nwd", "wiou+nwd"],
                     help="box loss mode (north-star: wiou+nwd; the reference's cfg default is ciou)")
+    ap.add_argument("--full", action="store_true", help="also measure the other loss mode, the roofline probe, the secondary workloads "
+                    "and the CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -296,12 +320,14 @@ def main():
     value = a.batch * world * a.steps / dt
     plan.check_progress()  # a step whose optimizer launches do not take effect (counter stuck, everything skipped) is not a number
     skipped_timed = float(plan.state[6]) - skipped_before
+    if rank == 0 and a.dump_outputs:  # before --full runs any further step
+        dump_outputs(a.dump_outputs, plan, model)
 
     # the reference-default CIoU loss beside the north-star's WIoU+NWD (or the other way round): same launch list, replayed
     # eagerly (the loss mode is a by-value launch argument, so it cannot change inside the captured graph)
     other = "ciou" if a.loss != "ciou" else "wiou+nwd"
     other_rate = None
-    if world == 1:
+    if world == 1 and a.full:
         g_fb, plan.graph_fb = plan.graph_fb, None
         try:
             plan.crit.bbox_loss.use_wiseiou, plan.crit.bbox_loss.nwd_loss = other.startswith("wiou"), other.endswith("nwd")
@@ -320,7 +346,7 @@ def main():
 
     roof = breakdown = None
     scalars_last, loss_scale, skipped_total = plan.crit.scalars.cpu(), float(plan.state[0]), float(plan.state[6])
-    if rank == 0 and a.probe:
+    if rank == 0 and a.full and a.probe:
         pr = plan.probe_dominant_kernel(batch, reps=max(5, min(a.steps, 20)))
         if pr:
             try:  # HBM bytes per launch from the rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes committed under profiles/
@@ -356,7 +382,7 @@ def main():
                     "ranking": pr["ranking"]}
             breakdown = plan.breakdown()
     secondary = None
-    if rank == 0 and world == 1 and a.secondary and a.model == "yolov8n-ASF-P2P2" and a.batch == 64 and a.imgsz == 640:
+    if rank == 0 and world == 1 and a.full and a.secondary and a.model == "yolov8n-ASF-P2P2" and a.batch == 64 and a.imgsz == 640:
         secondary = {}  # (the headline plan's buffers stay resident: 288 GB hold all three workloads)
         for key, fn in (("ld_train", secondary_ld), ("p2_1280_infer", secondary_p2_1280)):
             try:
@@ -365,7 +391,7 @@ def main():
                 secondary[key] = {"error": f"{type(e).__name__}: {e}"}
             print(f"[bench] secondary {key}: {secondary[key]}", file=sys.stderr, flush=True)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu:
         cpu = cpu_baseline(a.imgsz)
     if rank == 0:
         s = scalars_last

@@ -19,6 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
+os.environ["MKL_CBWR"] = "COMPATIBLE"  # MKL's processor-independent branch, as tests/conftest.py pins it for the tests
+
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 

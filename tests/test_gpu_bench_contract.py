@@ -1,10 +1,12 @@
-"""-m gpu: the driver's contract with bench.py -- ONE JSON line with the agreed keys, a `roofline` object priced on algorithmic
-bytes with the step-level fraction beside it, a `cpu_baseline` object from the oracle, and a value that follows from the timing."""
+"""-m gpu: the driver's contract with bench.py -- ONE JSON line with the agreed keys and a value that follows from the timing; with
+--full a `roofline` object priced on algorithmic bytes with the step-level fraction beside it and a `cpu_baseline` object from the
+oracle."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -13,8 +15,8 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_prints_one_contract_line():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "8", "--imgsz", "320", "--lr", "0.0005"],
-                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "8", "--imgsz", "320", "--lr", "0.0005",
+                        "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-1000:]
@@ -44,6 +46,30 @@ def test_bench_prints_one_contract_line():
     assert d["config"]["skipped_steps"] <= 8 and d["config"]["skipped_in_timed_steps"] == 0  # the loss-scale search ends before the timed steps
     assert d["config"]["capture_retries"] == 0  # one process on the GPU: the step graph verifies on its first capture
     assert d["config"]["loss_mode"] == "wiou+nwd" and d["config"]["ciou_images_per_s"] > 0 and c["bs16"] > 0
+
+
+def test_plain_bench_measures_the_headline_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline and nothing that takes runs of its own; --dump-outputs writes what the last
+    timed step computed as float32 arrays."""
+    out = tmp_path / "out"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8", "--imgsz", "320", "--lr", "0.0005",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-1000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "images/s" and d["dtype"] == "f16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 8 * 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"] and d["config"]["skipped_in_timed_steps"] == 0
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    assert d["config"]["secondary"] is None and d["config"]["device_ms_by_call"] is None and d["config"]["ciou_images_per_s"] is None
+    a = {f.name[:-len(".npy")]: np.load(f) for f in out.glob("*.npy")}
+    assert set(a) == {"loss_items", "loss", "params", "grads", "ema", "bn_stats"}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert sum(f.stat().st_size for f in out.glob("*.npy")) <= 64 << 20
+    n = 997202  # parameters of DEAL-YOLO-N (yolov8n-ASF-P2P2, nc 6)
+    assert a["loss_items"].shape == (3,) and a["params"].shape == a["grads"].shape == a["ema"].shape == (n,)
+    assert abs(a["loss"][0] - 8 * a["loss_items"].sum()) <= 1e-4 * abs(a["loss"][0])  # the loss kernel's total: (box + cls + dfl) * B
+    assert np.abs(a["grads"]).max() > 0 and not np.array_equal(a["params"], a["ema"])
 
 
 def test_bench_secondary_workloads_have_their_keys():

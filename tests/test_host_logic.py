@@ -111,11 +111,14 @@ def test_reference_format_checkpoint_roundtrip(tmp_path):
         assert torch.equal(a.half().float() if a.is_floating_point() else a, b if not b.is_floating_point() else b.float()), k
 
 
-def test_reference_entry_script_arguments_are_accepted():
+def test_reference_entry_script_arguments_are_accepted(tmp_path, monkeypatch):
     """The keyword sets of the reference's entry scripts (train.py:9-24, detect.py:7-14, val.py:8-16, get_FPS.py:40-52) pass the
     cfg check, device lists parse without touching a GPU, and the multi-GPU launch is the reference's torch.distributed.run
     command (utils/dist.py:47-65) around a script that rebuilds the model and calls train with the same overrides."""
     import ast
+    import tempfile
+    # the launch script goes under the temporary directory: this test's own, not a shared one another user may already own
+    monkeypatch.setattr(tempfile, "tempdir", str(tmp_path))
     from ultralytics.cfg import DEFAULT_CFG_DICT, get_cfg
     from ultralytics.utils.dist import ddp_cleanup, generate_ddp_command, parse_devices
     from ultralytics.utils.torch_utils import select_device

@@ -6,6 +6,7 @@
 #      SQ_LDS_BANK_CONFLICT + SQ_LDS_IDX_ACTIVE  (counters only with --kernel-trace: gpurun refuses other trace domains with --pmc)
 # usage: tools/collect_profiles.sh [extra bench.py arguments, e.g. --loss wiou+nwd]
 set -e
+set -- --full "$@"  # the bench runs below profile the roofline probe and the second loss mode beside the timed steps
 export DEBUG_CLR_GRAPH_PACKET_CAPTURE=0  # the profiler may initialise HIP before Python can set it (ultralytics/hip/__init__.py)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf gpurun_out/prof_stats gpurun_out/prof_fetch gpurun_out/prof_write gpurun_out/prof_mfma gpurun_out/prof_lds
