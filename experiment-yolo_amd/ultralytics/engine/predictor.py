@@ -147,7 +147,7 @@ class DetectionPredictor:
             t0 = time.perf_counter()
             im = self.preprocess(chunk)
             t1 = time.perf_counter()
-            preds = self.model(im)
+            preds = self.model(im, augment=bool(self.args.augment))  # engine/predictor.py:140
             if self.args.verbose:
                 torch.cuda.synchronize()
             t2 = time.perf_counter()

@@ -376,7 +376,7 @@ class DetectionTrainer:
         if self.args.val and self.rank == 0:
             vloader = self.get_dataloader(self.data["val"], batch_size * 2, 0, "val", self.data)
             self.validator = DetectionValidator(dataloader=vloader, args=self.args)
-            self.metrics = self.validator(model=self.ema.ema)
+            self.metrics = self.validator(trainer=self, model=self.ema.ema)  # a validation inside training: no TTA (validator.py:109)
         return hist
 
     def save_model(self, path, reference_format=False):

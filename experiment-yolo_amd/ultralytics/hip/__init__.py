@@ -174,6 +174,8 @@ SIGNATURES = {
     "dy_optimizer_step": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i32, vp]),
     "dy_optimizer_step_seg": (i32, [vp, vp, vp, vp, vp, i64, lp, vp, vp, vp, i64, vp, vp, vp, i32, vp]),
     "dy_axpy_f32": (i32, [vp, vp, f32, i64, vp]),
+    "dy_scale_img": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "dy_tta_merge": (i32, [i32, C.POINTER(vp), ip, ip, ip, C.POINTER(f32), ip, i32, i32, i32, i32, vp, vp]),
 }
 
 _LIB = None

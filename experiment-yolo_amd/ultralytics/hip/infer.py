@@ -115,19 +115,25 @@ def forward_eval(model, x):
     with torch.no_grad():
         if plan is not None:
             return plan(x), LazyFeats(plan.ho)
-        rt = model._runtime(x.device)
-        eng = rt.eng
-        eng.training = False
-        rt.ensure_packed()
-        eng.infer_head = True
-        try:
-            ho = model.forward_act(ImageAct(eng, x.float().contiguous()))
-        finally:
-            eng.infer_head = False
-        if ho.infer is not None:
-            return ho.infer(), LazyFeats(ho)
-        from ..utils.ops import decode_predictions
-        return decode_predictions(ho), LazyFeats(ho)
+        y, ho = walk_eval(model, x)
+        return y, LazyFeats(ho)
+
+
+def walk_eval(model, x):
+    """The eval forward's launches issued by walking the modules (no plan) -> (y, HeadOut)."""
+    rt = model._runtime(x.device)
+    eng = rt.eng
+    eng.training = False
+    rt.ensure_packed()
+    eng.infer_head = True
+    try:
+        ho = model.forward_act(ImageAct(eng, x.float().contiguous()))
+    finally:
+        eng.infer_head = False
+    if ho.infer is not None:
+        return ho.infer(), ho
+    from ..utils.ops import decode_predictions
+    return decode_predictions(ho), ho
 
 
 def plan_for(model, x):

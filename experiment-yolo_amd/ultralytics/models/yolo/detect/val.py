@@ -124,9 +124,10 @@ class DetectionValidator:
         self.device = next(model.parameters()).device if next(model.parameters()).is_cuda else select_device("0")
         model.to(self.device).eval()
         self.init_metrics(model)
+        augment = bool(self.args.augment) and trainer is None  # engine/validator.py:109: never while training
         for batch in self.dataloader:
             batch = self.preprocess(batch)
-            preds = self.postprocess(model(batch["img"]))
+            preds = self.postprocess(model(batch["img"], augment=augment))
             self.update_metrics(preds, batch)
         stats = self.get_stats()
         self.print_results()

@@ -147,7 +147,15 @@ class BaseModel(HipModule):
 
     def predict(self, x, profile=False, visualize=False, augment=False, embed=None):
         """Reference tasks.py:67-83.  In eval mode a detection model's forward of a (B, 3, H, W) device tensor goes through the
-        inference plan of its geometry (hip/infer.py: recorded launch list / hipGraph, stem from the image batch, fused Detect tail)."""
+        inference plan of its geometry (hip/infer.py: recorded launch list / hipGraph, stem from the image batch, fused Detect tail).
+        ``augment=True``: test-time augmentation (reference tasks.py:335-371, hip/tta.py) -> (y, None), eval mode only."""
+        if augment:
+            from ..hip.tta import forward_tta, wants_tta
+            if self.training:
+                raise NotImplementedError("augment=True (test-time augmentation) is an eval-mode forward: call model.eval() first")
+            if not wants_tta(self, x):
+                raise NotImplementedError("augment=True needs a detection model and a (B, 3, H, W) floating-point tensor on the GPU")
+            return forward_tta(self, x)
         if not self.training:
             from ..hip.infer import forward_eval, wants_plan
             if wants_plan(self, x):

@@ -86,15 +86,15 @@ def scale_boxes_vectorized(boxes, pad_x, pad_y, crop_info, ratio):
     return scaled
 
 
-def _second_stage(model, crops, conf, iou, batch_size):
-    """model.predict on every crop: forward + decode + soft-NMS, boxes clipped to the crop canvas (ops.scale_boxes with equal
-    shapes = clip_boxes)."""
+def _second_stage(model, crops, conf, iou, batch_size, augment=False):
+    """model.predict on every crop: forward (test-time augmented with ``augment``, :231/:235) + decode + soft-NMS, boxes clipped to
+    the crop canvas (ops.scale_boxes with equal shapes = clip_boxes)."""
     model.eval()
     preds = []
     with torch.no_grad():
         for i in range(0, crops.shape[0], batch_size):
             x = crops[i:i + batch_size].permute(0, 3, 1, 2).float() / 255
-            y, _ = model(x)
+            y, _ = model(x, augment=augment)
             for p in ops.non_max_suppression(y, conf, iou, max_det=300):
                 p[:, :4].clamp_(0, crops.shape[1])
                 preds.append(p)
@@ -106,8 +106,6 @@ def perform_batch_double_inference(image, model, detections, use_augment=False, 
     """:206-260.  image: (H,W,3) uint8 RGB (tensor | ndarray); detections: [{'bbox': [x1,y1,x2,y2], 'score', 'category_id'}].
     Returns ([refined dicts], seconds) like the reference -- only the successful refinements, in detection order -- or, with
     ``return_aligned``, one entry (dict | None) per detection."""
-    if use_augment:
-        raise NotImplementedError("test-time augmentation is not on the DEAL-YOLO hot path")
     t0 = time.time()
     dev = next(model.parameters()).device
     image = torch.as_tensor(image).to(dev).contiguous()
@@ -119,7 +117,8 @@ def perform_batch_double_inference(image, model, detections, use_augment=False, 
     if valid:
         cinfo = [crop_infos[k] for k in valid]
         crops, geos = prepare_cropped_images(image, cinfo)
-        preds = _second_stage(model, crops, conf, iou, batch_size)
+        args = (model, crops, conf, iou, batch_size)
+        preds = _second_stage(*args, augment=True) if use_augment else _second_stage(*args)
         K = len(valid)
         counts = [int(p.shape[0]) for p in preds]
         off = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int32, device=dev)

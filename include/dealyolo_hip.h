@@ -481,6 +481,19 @@ int dy_refine_select(const float* dets, const int* offsets, const float* orig, c
 int dy_nms_hard(const float* boxes, const float* scores, const float* labels, int n, float iou_thr, void* keep,
                 hipStream_t stream);
 
+/* ---- test-time augmentation, reference nn/tasks.py:335-371 (DetectionModel._predict_augment / _descale_pred / _clip_augmented) and
+ *      utils/torch_utils.py:355-366 (scale_img); the pass geometry is host arithmetic (ultralytics/hip/tta.py).
+ * scale_img of one pass in one launch: x (B, 3, H, W) fp32 NCHW -> out (B, 3, Hp, Wp) fp32 NCHW = x flipped (flip 0: none,
+ * 2: up-down, 3: left-right), resized into the top-left Ho x Wo with F.interpolate(mode='bilinear', align_corners=False) index
+ * arithmetic (sizes given, no scale factor), the rest filled with (float)0.447.  Ho <= Hp, Wo <= Wp; Ho == H and Wo == W copies. */
+int dy_scale_img(const float* x, int B, int H, int W, int flip, int Ho, int Wo, int Hp, int Wp, float* out, hipStream_t stream);
+/* _descale_pred + _clip_augmented + torch.cat(y, -1) of n_pass (<= 4) passes in one launch: pass k's output y_ptrs[k] (B, no, A[k])
+ * contributes its columns [col_lo[k], col_hi[k]) to out (B, no, sum_k (col_hi[k] - col_lo[k])), rows 0-3 divided by scale[k] (the
+ * correctly rounded quotient), then x = W - x for flip[k] == 3, y = H - y for flip[k] == 2; (H, W) is the original input size.
+ * Host arrays y_ptrs .. flip; out must not overlap any y. */
+int dy_tta_merge(int n_pass, const float* const* y_ptrs, const int* A, const int* col_lo, const int* col_hi, const float* scale,
+                 const int* flip, int B, int no, int H, int W, float* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
