@@ -1,3 +1,3 @@
 #include "common.h"
 #include "dealyolo_hip.h"
-extern "C" int dy_abi_version(void) { return 1; }
+extern "C" int dy_abi_version(void) { return 2; }

@@ -2,7 +2,9 @@
 // losses with ANALYTIC gradients w.r.t. the head logits -- no autograd graph, no (B, n_max, A) temporaries, no host
 // synchronisation.  Replaces v8DetectionLoss.__call__ (reference utils/loss.py:356-457), TaskAlignedAssigner.forward
 // (utils/tal.py:39-258), BboxLoss.forward (utils/loss.py:202-250), bbox_iou / wasserstein_loss / WiseIouLoss
-// (utils/metrics.py:75-126, 540-565, 591-645) and their backward.
+// (utils/metrics.py:75-126, 540-565, 591-645) and their backward.  The rest of the reference's box-loss menu -- every WiseIouLoss
+// ltype / focusing mechanism, the bbox_iou flags, Inner- / Focaler-IoU and MPDIoU (utils/metrics.py:75-741, utils/loss.py:199-217) --
+// runs in box_loss_kernel<true> (DyLossArgs.box_family != 0).
 //
 // Layout: per level l the head writes box logits fp32 (B,H,W,64) and class logits fp32 (B,H,W,ncp); anchors are
 // numbered level-major, row-major (utils/tal.py:294-307).  Box work maps ONE anchor to ONE wave: lane = side*16+bin,
@@ -29,6 +31,11 @@ struct Level {
   const float* w = nullptr;
   const float* bias = nullptr;
   const float* incoef = nullptr;  // non-null: xin is the RAW output of the Conv below ([4][64] scale, shift, ..): applied here
+};
+struct BoxMode {  // DyLossArgs.box_* (include/dealyolo_hip.h DY_BOX_*)
+  int family, ltype, fm, modifier;
+  float inner_ratio, focaler_d, focaler_u, shape_scale, piou_lambda;
+  float mpd_hw_num;  // img_h^2 + img_w^2: mpdiou_hw = mpd_hw_num / stride^2 (utils/loss.py:445)
 };
 struct LossCtx {
   Level lv[4];
@@ -58,6 +65,7 @@ struct LossCtx {
   float iou_ratio;
   const float* gscale;  // device scalar multiplied into every gradient (loss scale)
   int prob_scores;      // lv[].cls holds sigmoid probabilities (dy_tal_assign: TaskAlignedAssigner.forward's pd_scores), not logits
+  BoxMode bm;           // extended box loss (DyLossArgs.box_*); family 0 = the legacy modes, read by box_loss_kernel<true> only
 };
 
 static __device__ __forceinline__ void anchor_of(const LossCtx& c, int a, int& l, int& iy, int& ix) {
@@ -138,6 +146,46 @@ static __device__ __forceinline__ Dual t_sqrt(Dual a) { const float s = sqrtf(a.
 static __device__ __forceinline__ float lift(float, float v) { return v; }
 static __device__ __forceinline__ Dual lift(Dual, float v) { return dconst(v); }
 
+// ---- primitives of the extended box-loss family (box_loss_kernel<true>).  Subgradients at kinks follow torch: abs'(0) = 0, clamp
+// passes no gradient outside [lo, hi] (and passes it on the bounds), relu'(0) = 0, torch.maximum / minimum split the gradient 1/2 : 1/2
+// on an exact tie, min(dim) sends it to the first minimum (dmin above).
+static __device__ __forceinline__ Dual operator-(Dual a) { return a * -1.f; }
+static __device__ __forceinline__ Dual operator-(Dual a, float b) { a.v -= b; return a; }
+static __device__ __forceinline__ Dual operator-(float a, Dual b) { return -b + a; }
+static __device__ __forceinline__ Dual operator*(float a, Dual b) { return b * a; }
+static __device__ __forceinline__ Dual operator/(Dual a, float b) {  // reciprocal form, as operator/(Dual, Dual)
+  const float q = a.v / b, inv = 1.0f / b;
+  Dual r{q, {}};
+  for (int i = 0; i < 4; ++i) r.d[i] = a.d[i] * inv;
+  return r;
+}
+static __device__ __forceinline__ Dual dsel(bool p, Dual a, Dual b) {  // torch.where: the unselected branch gets no gradient
+  Dual r{p ? a.v : b.v, {}};
+  for (int i = 0; i < 4; ++i) r.d[i] = p ? a.d[i] : b.d[i];
+  return r;
+}
+static __device__ __forceinline__ Dual dmaximum(Dual a, Dual b) {
+  return a.v == b.v ? (a + b) * 0.5f : dsel(a.v > b.v, a, b);
+}
+static __device__ __forceinline__ Dual dminimum(Dual a, Dual b) {
+  return a.v == b.v ? (a + b) * 0.5f : dsel(a.v < b.v, a, b);
+}
+static __device__ __forceinline__ Dual dclamp(Dual a, float lo, float hi) {
+  Dual r{fminf(fmaxf(a.v, lo), hi), {}};
+  const bool in = a.v >= lo && a.v <= hi;
+  for (int i = 0; i < 4; ++i) r.d[i] = in ? a.d[i] : 0.f;
+  return r;
+}
+static __device__ __forceinline__ Dual dabs(Dual a) { return dfn(a, fabsf(a.v), a.v > 0.f ? 1.f : (a.v < 0.f ? -1.f : 0.f)); }
+static __device__ __forceinline__ Dual dsq(Dual a) { return dfn(a, a.v * a.v, 2.f * a.v); }
+static __device__ __forceinline__ Dual dpow4(Dual a) { const float s = a.v * a.v; return dfn(a, s * s, 4.f * s * a.v); }
+static __device__ __forceinline__ Dual dasin(Dual a) { return dfn(a, asinf(a.v), 1.f / sqrtf(1.f - a.v * a.v)); }
+static __device__ __forceinline__ Dual dsin(Dual a) { return dfn(a, sinf(a.v), cosf(a.v)); }
+static __device__ __forceinline__ Dual dcos(Dual a) { return dfn(a, cosf(a.v), -sinf(a.v)); }
+static __device__ __forceinline__ float dsel_d(const Dual& a, int i) {  // a.d[i] without a lane-varying index into the array
+  return i == 0 ? a.d[0] : (i == 1 ? a.d[1] : (i == 2 ? a.d[2] : a.d[3]));
+}
+
 // bbox_iou(box1, box2, xywh=False, CIoU=True), utils/metrics.py:75-126.  T = float (assigner) or Dual (loss).
 template <typename T>
 static __device__ __forceinline__ T ciou_t(T x1, T y1, T x2, T y2, float X1, float Y1, float X2, float Y2) {
@@ -162,6 +210,208 @@ static __device__ __forceinline__ T ciou_t(T x1, T y1, T x2, T y2, float X1, flo
 // swapped inside v; v is symmetric, eps placement is identical, so one routine serves both.
 static __device__ __forceinline__ float ciou_gt_pred(const float* g, const float* p) {
   return ciou_t<float>(g[0], g[1], g[2], g[3], p[0], p[1], p[2], p[3]);
+}
+
+// ---------------------------------------------------------------------------------------------- extended box-loss family
+// (x1,y1,x2,y2) = predicted box (Dual), t = target box, both in grid units, as BboxLoss.forward receives them (utils/loss.py:444).
+static __device__ __forceinline__ Dual dclamp0(Dual a) { return dclamp(a, 0.f, __builtin_inff()); }  // .clamp_(0)
+
+// get_inner_iou(pred, target, xywh=False, ratio) (utils/metrics.py:186-218): both boxes scaled by ratio about their centres, +eps union
+static __device__ __forceinline__ Dual inner_iou(Dual x1, Dual y1, Dual x2, Dual y2, const float* t, float ratio) {
+  const Dual cx = (x1 + x2) / 2.f, cy = (y1 + y2) / 2.f, w = x2 - x1, h = y2 - y1;
+  const float tcx = (t[0] + t[2]) / 2.f, tcy = (t[1] + t[3]) / 2.f, tw = t[2] - t[0], th = t[3] - t[1];
+  const Dual hw = (w * ratio) / 2.f, hh = (h * ratio) / 2.f;
+  const float thw = (tw * ratio) / 2.f, thh = (th * ratio) / 2.f;
+  const Dual iw = dclamp0(dminimum(cx + hw, dconst(tcx + thw)) - dmaximum(cx - hw, dconst(tcx - thw)));
+  const Dual ih = dclamp0(dminimum(cy + hh, dconst(tcy + thh)) - dmaximum(cy - hh, dconst(tcy - thh)));
+  const Dual inter = iw * ih;
+  const Dual uni = ((w * h * ratio * ratio) + (tw * th * ratio * ratio) - inter) + IOU_EPS;
+  return inter / uni;
+}
+
+// WiseIouLoss's 'iou' entry (utils/metrics.py:618): 1 - IoU, 1 - Inner-IoU or 1 - Focaler-IoU.  inter / uni: s_inter / s_union (no eps).
+static __device__ __forceinline__ Dual wise_liou(Dual x1, Dual y1, Dual x2, Dual y2, const float* t, const BoxMode& m, Dual inter,
+                                                 Dual uni) {
+  if (m.modifier == DY_BOX_MOD_INNER) return 1.f - inner_iou(x1, y1, x2, y2, t, m.inner_ratio);
+  const Dual r = inter / uni;
+  if (m.modifier == DY_BOX_MOD_FOCALER) return 1.f - dclamp((r - m.focaler_d) / (m.focaler_u - m.focaler_d), 0.f, 1.f);
+  return 1.f - r;
+}
+static __device__ __forceinline__ void wise_inter_union(Dual x1, Dual y1, Dual x2, Dual y2, const float* t, Dual& inter, Dual& uni) {
+  const Dual iw = drelu(dminimum(x2, dconst(t[2])) - dmaximum(x1, dconst(t[0])));
+  const Dual ih = drelu(dminimum(y2, dconst(t[3])) - dmaximum(y1, dconst(t[1])));
+  inter = iw * ih;
+  uni = ((x2 - x1) * (y2 - y1) + (t[2] - t[0]) * (t[3] - t[1])) - inter;
+}
+// the value alone (tal_scores_kernel's running-mean sum)
+static __device__ __forceinline__ float wise_liou_value(const float* p, const float* t, const BoxMode& m) {
+  const Dual x1 = dconst(p[0]), y1 = dconst(p[1]), x2 = dconst(p[2]), y2 = dconst(p[3]);
+  Dual inter, uni;
+  wise_inter_union(x1, y1, x2, y2, t, inter, uni);
+  return wise_liou(x1, y1, x2, y2, t, m, inter, uni).v;
+}
+
+// WiseIouLoss.forward (utils/metrics.py:591-638) for one box pair: _<ltype>(**kwargs), then _scaled_loss.  iou_mean: after this call's
+// update (the reference updates it first, :621-623).  hw: mpdiou_hw of the anchor's level.
+static __device__ __forceinline__ Dual wise_loss(Dual x1, Dual y1, Dual x2, Dual y2, const float* t, const BoxMode& m, float iou_mean,
+                                                 float hw) {
+  Dual inter, uni;
+  wise_inter_union(x1, y1, x2, y2, t, inter, uni);
+  const Dual li = wise_liou(x1, y1, x2, y2, t, m, inter, uni);
+  const Dual pw = x2 - x1, ph = y2 - y1;
+  const float tw = t[2] - t[0], th = t[3] - t[1];
+  const Dual bw = dmaximum(x2, dconst(t[2])) - dminimum(x1, dconst(t[0]));  // wh_box
+  const Dual bh = dmaximum(y2, dconst(t[3])) - dminimum(y1, dconst(t[1]));
+  const Dual dcx = (x1 + x2) / 2.f - (t[0] + t[2]) / 2.f, dcy = (y1 + y2) / 2.f - (t[1] + t[3]) / 2.f;  // d_center
+  const Dual l2c = dsq(dcx) + dsq(dcy);
+  Dual l;
+  switch (m.ltype) {
+    case DY_BOX_WIOU:  // l2_box detached
+      l = t_exp(l2c / (bw.v * bw.v + bh.v * bh.v)) * li;
+      break;
+    case DY_BOX_EIOU:
+      l = li + (l2c / (dsq(bw) + dsq(bh)) + (dsq(dcx / bw) + dsq(dcy / bh)));
+      break;
+    case DY_BOX_GIOU: {
+      const Dual sbox = bw * bh;
+      l = li + (sbox - uni) / sbox;
+      break;
+    }
+    case DY_BOX_DIOU:
+      l = li + l2c / (dsq(bw) + dsq(bh));
+      break;
+    case DY_BOX_CIOU: {  // eps 1e-4 in the atan terms; alpha detached
+      const Dual v = dsq(t_atan(pw / (ph + 1e-4f)) - atanf(tw / (th + 1e-4f))) * (float)(4.0 / (M_PI * M_PI));
+      const float alpha = v.v / (li.v + v.v);
+      l = (li + l2c / (dsq(bw) + dsq(bh))) + v * alpha;
+      break;
+    }
+    case DY_BOX_SIOU: {  // theta 4; 1e-4 on sqrt(l2_center); min(dim) -> first minimum
+      const Dual ang = dsin(2.f * dasin(dmin(dabs(dcx), dabs(dcy)) / (t_sqrt(l2c) + 1e-4f))) - 2.f;
+      const Dual dist = (2.f - t_exp(ang * dsq(dcx / bw))) - t_exp(ang * dsq(dcy / bh));
+      const Dual ws = 1.f - t_exp(-dabs(pw - tw) / dmaximum(pw, dconst(tw)));
+      const Dual hs = 1.f - t_exp(-dabs(ph - th) / dmaximum(ph, dconst(th)));
+      l = li + (dist + (dpow4(ws) + dpow4(hs))) / 2.f;
+      break;
+    }
+    case DY_BOX_MPDIOU: {
+      const Dual d1 = dsq(t[0] - x1) + dsq(t[1] - y1), d2 = dsq(t[2] - x2) + dsq(t[3] - y2);
+      l = (li + d1 / hw) + d2 / hw;
+      break;
+    }
+    case DY_BOX_SHAPEIOU: {  // 1e-7 in h and c2
+      const Dual w1 = pw, h1 = ph + 1e-7f;
+      const float w2 = tw, h2 = th + 1e-7f;
+      const float pws = powf(w2, m.shape_scale), phs = powf(h2, m.shape_scale);
+      const float ww = 2.f * pws / (pws + phs), hh = 2.f * phs / (pws + phs);
+      const Dual c2 = (dsq(bw) + dsq(bh)) + 1e-7f;
+      const Dual cdx = dsq(((t[0] + t[2]) - x1) - x2) / 4.f, cdy = dsq(((t[1] + t[3]) - y1) - y2) / 4.f;
+      const Dual dist = (hh * cdx + ww * cdy) / c2;
+      const Dual ow = (hh * dabs(w1 - w2)) / dmaximum(w1, dconst(w2)), oh = (ww * dabs(h1 - h2)) / dmaximum(h1, dconst(h2));
+      const Dual shape = dpow4(1.f - t_exp(-ow)) + dpow4(1.f - t_exp(-oh));
+      l = (li + dist) + 0.5f * shape;
+      break;
+    }
+    case DY_BOX_PIOU:
+    case DY_BOX_PIOU2: {  // 1e-7 in h
+      const float w2 = tw, h2 = th + 1e-7f;
+      const Dual dw1 = dabs(dminimum(x2, x1) - fminf(t[2], t[0])), dw2 = dabs(dmaximum(x2, x1) - fmaxf(t[2], t[0]));
+      const Dual dh1 = dabs(dminimum(y2, y1) - fminf(t[3], t[1])), dh2 = dabs(dmaximum(y2, y1) - fmaxf(t[3], t[1]));
+      const Dual P = ((dw1 + dw2) / fabsf(w2) + (dh1 + dh2) / fabsf(h2)) / 4.f;
+      const Dual pv1 = (li - t_exp(-dsq(P))) + 1.f;
+      if (m.ltype == DY_BOX_PIOU) {
+        l = pv1;
+      } else {
+        const Dual x = t_exp(-P) * m.piou_lambda;
+        l = ((3.f * x) * t_exp(-dsq(x))) * pv1;
+      }
+      break;
+    }
+    default:  // DY_BOX_IOU
+      l = li;
+  }
+  if (m.fm == DY_BOX_FM_V2) {  // _scaled_loss, beta detached
+    l = l * sqrtf(li.v / iou_mean);
+  } else if (m.fm == DY_BOX_FM_V3) {
+    const float beta = li.v / iou_mean;
+    l = l * (beta / (2.7f * powf(1.7f, beta - 2.7f)));
+  }
+  return l;
+}
+
+// bbox_iou / bbox_inner_iou / bbox_focaler_iou (utils/metrics.py:75-444) with one flag, or bbox_{,inner_,focaler_}mpdiou (:446-538);
+// xywh=False, eps=1e-7.  The loss is (1 - this) * weight (utils/loss.py:218).
+static __device__ __forceinline__ Dual bbox_family_iou(Dual x1, Dual y1, Dual x2, Dual y2, const float* t, const BoxMode& m, float hw) {
+  const Dual w1 = x2 - x1, h1 = (y2 - y1) + IOU_EPS;
+  const float w2 = t[2] - t[0], h2 = (t[3] - t[1]) + IOU_EPS;
+  const Dual iw = dclamp0(dminimum(x2, dconst(t[2])) - dmaximum(x1, dconst(t[0])));
+  const Dual ih = dclamp0(dminimum(y2, dconst(t[3])) - dmaximum(y1, dconst(t[1])));
+  const Dual inter = iw * ih;
+  const Dual uni = ((w1 * h1 + (w2 * h2)) - inter) + IOU_EPS;
+  const Dual iou = inter / uni;
+  Dual I = iou;   // what the return line subtracts from
+  Dual Ia = iou;  // what CIoU's alpha reads: the plain iou in bbox_inner_iou, the Focaler one in bbox_focaler_iou
+  if (m.modifier == DY_BOX_MOD_INNER) {
+    I = inner_iou(x1, y1, x2, y2, t, m.inner_ratio);
+  } else if (m.modifier == DY_BOX_MOD_FOCALER) {
+    I = Ia = dclamp((iou - m.focaler_d) / (m.focaler_u - m.focaler_d), 0.f, 1.f);
+  }
+  if (m.ltype == DY_BOX_IOU) return I;
+  if (m.ltype == DY_BOX_MPDIOU) {
+    const Dual d1 = dsq(t[0] - x1) + dsq(t[1] - y1), d2 = dsq(t[2] - x2) + dsq(t[3] - y2);
+    return (I - d1 / hw) - d2 / hw;
+  }
+  const Dual cw = dmaximum(x2, dconst(t[2])) - dminimum(x1, dconst(t[0]));
+  const Dual ch = dmaximum(y2, dconst(t[3])) - dminimum(y1, dconst(t[1]));
+  if (m.ltype == DY_BOX_GIOU) {
+    const Dual ca = cw * ch + IOU_EPS;
+    return I - (ca - uni) / ca;
+  }
+  const Dual c2 = (dsq(cw) + dsq(ch)) + IOU_EPS;
+  const Dual sx = ((t[0] + t[2]) - x1) - x2, sy = ((t[1] + t[3]) - y1) - y2;  // b2_x1 + b2_x2 - b1_x1 - b1_x2
+  const Dual rho2 = (dsq(sx) + dsq(sy)) / 4.f;
+  switch (m.ltype) {
+    case DY_BOX_CIOU: {
+      const Dual v = (float)(4.0 / (M_PI * M_PI)) * dsq(atanf(w2 / h2) - t_atan(w1 / h1));
+      const float alpha = v.v / ((v.v - Ia.v) + (1.f + IOU_EPS));
+      return I - (rho2 / c2 + v * alpha);
+    }
+    case DY_BOX_EIOU: {
+      const Dual rw2 = dsq((t[2] - t[0]) - (x2 - x1)), rh2 = dsq((t[3] - t[1]) - (y2 - y1));
+      return I - ((rho2 / c2 + rw2 / (dsq(cw) + IOU_EPS)) + rh2 / (dsq(ch) + IOU_EPS));
+    }
+    case DY_BOX_SIOU: {
+      const Dual scw = sx * 0.5f + IOU_EPS, sch = sy * 0.5f + IOU_EPS;
+      const Dual sigma = t_sqrt(dsq(scw) + dsq(sch));
+      const Dual s1 = dabs(scw) / sigma, s2 = dabs(sch) / sigma;
+      const Dual sa = dsel(s1.v > 0.70710678118654752f, s2, s1);
+      const Dual gamma = dcos(dasin(sa) * 2.f - (float)(M_PI / 2)) - 2.f;
+      const Dual dc = (2.f - t_exp(gamma * dsq(scw / cw))) - t_exp(gamma * dsq(sch / ch));
+      const Dual ow = dabs(w1 - w2) / dmaximum(w1, dconst(w2)), oh = dabs(h1 - h2) / dmaximum(h1, dconst(h2));
+      const Dual sc = dpow4(1.f - t_exp(-ow)) + dpow4(1.f - t_exp(-oh));
+      return (I - 0.5f * (dc + sc)) + IOU_EPS;
+    }
+    case DY_BOX_SHAPEIOU: {
+      const float pws = powf(w2, m.shape_scale), phs = powf(h2, m.shape_scale);
+      const float ww = 2.f * pws / (pws + phs), hh = 2.f * phs / (pws + phs);
+      const Dual dist = (hh * (dsq(sx) / 4.f) + ww * (dsq(sy) / 4.f)) / c2;
+      const Dual ow = (hh * dabs(w1 - w2)) / dmaximum(w1, dconst(w2)), oh = (ww * dabs(h1 - h2)) / dmaximum(h1, dconst(h2));
+      const Dual sc = dpow4(1.f - t_exp(-ow)) + dpow4(1.f - t_exp(-oh));
+      return (I - dist) - 0.5f * sc;
+    }
+    case DY_BOX_PIOU:
+    case DY_BOX_PIOU2: {
+      const Dual dw1 = dabs(dminimum(x2, x1) - fminf(t[2], t[0])), dw2 = dabs(dmaximum(x2, x1) - fmaxf(t[2], t[0]));
+      const Dual dh1 = dabs(dminimum(y2, y1) - fminf(t[3], t[1])), dh2 = dabs(dmaximum(y2, y1) - fmaxf(t[3], t[1]));
+      const Dual P = ((dw1 + dw2) / fabsf(w2) + (dh1 + dh2) / fabsf(h2)) / 4.f;
+      const Dual pv1 = ((1.f - I) - t_exp(-dsq(P))) + 1.f;
+      if (m.ltype == DY_BOX_PIOU) return 1.f - pv1;
+      const Dual x = t_exp(-P) * m.piou_lambda;
+      return 1.f - ((3.f * x) * t_exp(-dsq(x))) * pv1;
+    }
+    default:  // DY_BOX_DIOU
+      return I - rho2 / c2;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------- 1. targets
@@ -466,7 +716,8 @@ __global__ __launch_bounds__(256) void tal_scores_kernel(LossCtx c) {
         const float s = c.lv[l].stride;
         const float* g = c.gt_box + ((size_t)b * c.nmax + j) * 4;
         const float t[4] = {g[0] / s, g[1] / s, g[2] / s, g[3] / s};
-        s_li += liou_plain(c.pred_box + ba * 4, t);
+        // the running mean follows the modified iou (inner / focaler) in the extended Wise family, utils/metrics.py:618-623
+        s_li += c.bm.family == DY_BOX_FAMILY_WISE ? wise_liou_value(c.pred_box + ba * 4, t, c.bm) : liou_plain(c.pred_box + ba * 4, t);
       }
       s_n += 1.f;
     }
@@ -558,6 +809,9 @@ __global__ __launch_bounds__(256) void cls_loss_kernel(LossCtx c, int level) {
 }
 
 // ---------------------------------------------------------------------------------------------- 7. box + DFL loss
+// EXT = false: the four legacy modes (use_wiou / use_nwd), the instantiation as it always was.  EXT = true: the extended family
+// (DyLossArgs.box_family != 0) -- a separate instantiation so that the legacy one keeps its code.
+template <bool EXT>
 __global__ __launch_bounds__(256) void box_loss_kernel(LossCtx c) {
   const int lane = threadIdx.x & 63, side = lane >> 4, bin = lane & 15;
   const long wave = ((long)blockIdx.x * 256 + threadIdx.x) >> 6, nw = ((long)gridDim.x * 256) >> 6;
@@ -614,7 +868,13 @@ __global__ __launch_bounds__(256) void box_loss_kernel(LossCtx c) {
     // ---- IoU-family loss with forward-mode derivatives w.r.t. (x1,y1,x2,y2)
     Dual x1 = dvar(pb[0], 0), y1 = dvar(pb[1], 1), x2 = dvar(pb[2], 2), y2 = dvar(pb[3], 3);
     Dual lb;
-    if (c.use_wiou) {  // WiseIouLoss._WIoU + _scaled_loss (non-monotonous v3)
+    if constexpr (EXT) {
+      const float hw = c.bm.mpd_hw_num / (s * s);  // mpdiou_hw, utils/loss.py:445
+      if (c.bm.family == DY_BOX_FAMILY_WISE)
+        lb = wise_loss(x1, y1, x2, y2, t, c.bm, c.scal[4], hw);
+      else
+        lb = 1.f - bbox_family_iou(x1, y1, x2, y2, t, c.bm, hw);
+    } else if (c.use_wiou) {  // WiseIouLoss._WIoU + _scaled_loss (non-monotonous v3)
       const Dual pw = x2 - x1, ph = y2 - y1;
       const float tw = t[2] - t[0], th = t[3] - t[1];
       const Dual iw = drelu(dmin(x2, dconst(t[2])) - dmax(x1, dconst(t[0])));
@@ -647,7 +907,12 @@ __global__ __launch_bounds__(256) void box_loss_kernel(LossCtx c) {
     }
     const float kb = w / tss;  // (loss * weight).sum() / target_scores_sum
     // d(loss_box)/d(pred coord) -> d/dE (E = expected distance of this side): x1 = ax - E0, y1 = ay - E1, x2 = ax + E2 ...
-    const float dcoord = lb.d[side] * (side < 2 ? -1.f : 1.f);
+    float dlb;
+    if constexpr (EXT)
+      dlb = dsel_d(lb, side);
+    else
+      dlb = lb.d[side];
+    const float dcoord = dlb * (side < 2 ? -1.f : 1.f);
     float glogit = c.hyp_box * Bf * kb * dcoord * pr * ((float)bin - e);
     // ---- DFL (utils/loss.py:236-250, bbox2dist utils/tal.py:321-324)
     const float anc = (side & 1) ? (iy + 0.5f) : (ix + 0.5f);
@@ -823,6 +1088,17 @@ extern "C" int dy_detection_loss(const DyLossArgs* d, hipStream_t stream) {
   float* partC = (float*)take(4 * 4096 * 4);
   c.hyp_box = d->hyp_box; c.hyp_cls = d->hyp_cls; c.hyp_dfl = d->hyp_dfl;
   c.use_wiou = d->use_wiou; c.use_nwd = d->use_nwd; c.iou_ratio = d->iou_ratio; c.gscale = d->gscale;
+  if (d->box_family != DY_BOX_FAMILY_LEGACY) {
+    const int fam = d->box_family, lt = d->box_ltype, mod = d->box_modifier;
+    if (fam != DY_BOX_FAMILY_WISE && fam != DY_BOX_FAMILY_BBOX) return DY_ERR_ARG;
+    if (lt < DY_BOX_IOU || lt > DY_BOX_MPDIOU || (fam == DY_BOX_FAMILY_BBOX && lt == DY_BOX_WIOU)) return DY_ERR_ARG;
+    if (mod < DY_BOX_MOD_PLAIN || mod > DY_BOX_MOD_FOCALER) return DY_ERR_ARG;
+    if (fam == DY_BOX_FAMILY_WISE && (d->box_fm < DY_BOX_FM_V1 || d->box_fm > DY_BOX_FM_V3)) return DY_ERR_ARG;
+    if (mod == DY_BOX_MOD_FOCALER && !(d->focaler_u != d->focaler_d)) return DY_ERR_ARG;
+    c.bm = BoxMode{fam, lt, d->box_fm, mod, d->inner_ratio, d->focaler_d, d->focaler_u, d->shape_scale, d->piou_lambda,
+                   d->img_h * d->img_h + d->img_w * d->img_w};
+    c.use_wiou = fam == DY_BOX_FAMILY_WISE;  // the running mean is updated by every Wise call, v1 included (utils/metrics.py:621-623)
+  }
 
   hipLaunchKernelGGL(pack_targets_kernel, dim3(1), dim3(1024), 0, stream, c, d->t_batch_idx, d->t_cls, d->t_boxes,
                      d->n_targets, d->n_targets_dev, d->img_w, d->img_h);
@@ -851,7 +1127,10 @@ extern "C" int dy_detection_loss(const DyLossArgs* d, hipStream_t stream) {
   for (int l = 0; l < c.nl; ++l)  // background anchors get zero box-gradient: one memset instead of 2 M scattered stores
     if (c.lv[l].dbox && !d->dbox_rows_only && hipMemsetAsync(c.lv[l].dbox, 0, (size_t)c.B * c.lv[l].H * c.lv[l].W * 64 * 2, stream) != hipSuccess)
       return DY_ERR_LAUNCH;
-  hipLaunchKernelGGL(box_loss_kernel, dim3(gridA), dim3(256), 0, stream, c);
+  if (c.bm.family != DY_BOX_FAMILY_LEGACY)
+    hipLaunchKernelGGL(box_loss_kernel<true>, dim3(gridA), dim3(256), 0, stream, c);
+  else
+    hipLaunchKernelGGL(box_loss_kernel<false>, dim3(gridA), dim3(256), 0, stream, c);
   hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, stream, c, partB, gridA, partC, n_cls);
   DY_CHECK_LAUNCH();
   return DY_OK;

@@ -20,7 +20,7 @@ CFG_FRACTION_KEYS = ("dropout", "iou", "lr0", "lrf", "momentum", "weight_decay",
 CFG_INT_KEYS = ("epochs", "patience", "batch", "workers", "seed", "close_mosaic", "max_det", "vid_stride", "nbs", "save_period", "mask_ratio",
                 "nmax")
 CFG_BOOL_KEYS = ("save", "exist_ok", "verbose", "deterministic", "single_cls", "rect", "cos_lr", "amp", "val", "half",
-                 "agnostic_nms", "plots", "wiou", "nwd", "hipgraph", "multi_scale", "overlap_mask")
+                 "agnostic_nms", "plots", "wiou", "nwd", "hipgraph", "multi_scale", "overlap_mask", "wiou_inner", "wiou_focaler")
 
 
 class IterableSimpleNamespace(SimpleNamespace):

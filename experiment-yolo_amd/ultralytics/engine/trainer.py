@@ -94,6 +94,7 @@ class DetectionTrainer:
         self.gs = max(int(self.model.stride.max()), 32)  # reference engine/trainer.py:677: grid size, never below 32
         bl = self.plan.crit.bbox_loss
         bl.use_wiseiou, bl.nwd_loss, bl.iou_ratio = bool(a.wiou), bool(a.nwd), float(a.iou_ratio)
+        bl.configure_from_cfg(a)
         self.ema = ModelEMA(self.plan)
         self.nb = batches_per_epoch
         self.nw = max(round(a.warmup_epochs * self.nb), 100) if a.warmup_epochs > 0 else -1

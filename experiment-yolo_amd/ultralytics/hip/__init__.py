@@ -53,7 +53,10 @@ class DyLossArgs(C.Structure):
                 ("img_w", f32), ("img_h", f32), ("hyp_box", f32), ("hyp_cls", f32), ("hyp_dfl", f32),
                 ("use_wiou", i32), ("use_nwd", i32), ("iou_ratio", f32), ("gscale", vp), ("scalars", vp),
                 ("workspace", vp), ("dbox_rows_only", i32), ("box_from_input", i32), ("box_in", vp * 4), ("box_in_ld", i32 * 4),
-                ("box_w", vp * 4), ("box_b", vp * 4), ("box_in_coef", vp * 4)]
+                ("box_w", vp * 4), ("box_b", vp * 4), ("box_in_coef", vp * 4),
+                # extended box loss (DY_BOX_*): all zero = the legacy modes
+                ("box_family", i32), ("box_ltype", i32), ("box_fm", i32), ("box_modifier", i32), ("inner_ratio", f32),
+                ("focaler_d", f32), ("focaler_u", f32), ("shape_scale", f32), ("piou_lambda", f32)]
 
 
 class DySegs(C.Structure):

@@ -205,6 +205,7 @@ class StepPlan:
             raise RuntimeError(f"{n} targets exceed the plan capacity {self.B}x{self.nmax}")
         self.crit.sync_modes()
         if self.rec_fb is None:
+            self._box_mode = self.crit.bbox_loss.mode_fields()  # what a captured graph freezes (the launch takes the block by value)
             pre = (self.rt.flat_b.clone(), self.crit.scalars.clone()) if self.use_graph else None
             self.rec_fb = self._trace_fb(batch)
             if self.use_graph:
@@ -252,6 +253,7 @@ class StepPlan:
             if self.fb_cut is not None:
                 self._start_bucket1()  # the traced step ran whole: its first bucket starts now (nothing left to overlap with)
         elif self.fb_cut is not None:
+            self._check_box_mode()
             if self.graph_fb is not None:
                 self.graph_fb.replay()
             else:
@@ -262,10 +264,22 @@ class StepPlan:
             else:
                 self.eng.replay(self.rec_fb, self.fb_cut, None)
         elif self.graph_fb is not None:
+            self._check_box_mode()
             self.graph_fb.replay()
         else:
             self.eng.replay(self.rec_fb)
         return self.crit.scalars
+
+    def _check_box_mode(self):
+        """A captured graph replays the box loss it was captured with.  The legacy toggles (use_wiseiou / nwd_loss) keep their
+        behaviour -- frozen at capture -- but an extended mode (DyLossArgs.box_family != 0) that differs from the captured one,
+        on either side, raises instead of silently replaying the old loss."""
+        if self.graph_fb is None:
+            return
+        now, cap = self.crit.bbox_loss.mode_fields(), getattr(self, "_box_mode", None)
+        if cap is not None and now != cap and (now[0] or cap[0]):
+            raise RuntimeError(f"StepPlan: the box loss changed since the step was captured into a hipGraph ({cap} -> {now}); "
+                               "the graph would replay the old loss: build a new StepPlan (or use_graph=False) to change it")
 
     # ---- gradient buckets ------------------------------------------------------------------------------------------------------
     # The flat gradient buffer is laid out [neck + head | backbone | buffer tail] (hip/runtime.py), so a bucket is a VIEW of it: no

@@ -2,7 +2,8 @@
 
 ``v8DetectionLoss(model)(preds, batch)`` keeps the reference protocol and attribute names -- ``crit.bbox_loss.use_wiseiou``,
 ``crit.bbox_loss.nwd_loss``, ``crit.bbox_loss.iou_ratio`` toggle WIoU-v3 / NWD exactly as editing the two literals at
-loss.py:194,197 does in the reference, and ``crit.bbox_loss.wiou_loss.iou_mean`` is the WIoU running mean -- but the
+loss.py:194,197 does in the reference, ``crit.bbox_loss.wiou_loss = WiseIouLoss(...)``, ``.iou_type`` and ``.iou_variant`` pick
+any other box loss of the reference's menu (loss.py:199-217), and ``crit.bbox_loss.wiou_loss.iou_mean`` is the WIoU running mean -- but the
 whole computation (target packing, DFL decode, task-aligned assignment, BCE/CIoU|WIoU/NWD/DFL and the gradients w.r.t.
 the head logits) is one C-ABI call, ``dy_detection_loss``.
 """
@@ -31,15 +32,84 @@ class _WiouState:
         self._s[4] = float(v)
 
 
+# include/dealyolo_hip.h DY_BOX_* codes
+_LTYPE = {"IoU": 0, "WIoU": 1, "EIoU": 2, "GIoU": 3, "DIoU": 4, "CIoU": 5, "SIoU": 6, "ShapeIoU": 7, "PIoU": 8, "PIoU2": 9, "MPDIoU": 10}
+IOU_TYPES = tuple(k for k in _LTYPE if k != "WIoU")
+IOU_VARIANTS = (None, "inner", "focaler")
+
+
 class BboxLoss:
-    """Toggle holder mirroring reference ``BboxLoss.__init__`` (utils/loss.py:189-200)."""
+    """Toggle holder mirroring reference ``BboxLoss.__init__`` (utils/loss.py:189-200).
+
+    The box-loss menu of the reference's call sites (utils/loss.py:199-217): with ``use_wiseiou`` the loss is ``wiou_loss``, a
+    ``WiseIouLoss(ltype, monotonous, inner_iou, focaler_iou)`` (utils/metrics.py:567); without it, ``(1 - iou) * weight`` with
+    ``iou_type`` one of IOU_TYPES (the bbox_iou flag, or bbox_mpdiou) and ``iou_variant`` None (bbox_iou), 'inner'
+    (bbox_inner_*) or 'focaler' (bbox_focaler_*).  ``inner_ratio``, ``focaler_d``, ``focaler_u``, ``shape_scale`` and
+    ``piou_lambda`` are the keyword arguments of those calls, at the call sites' values by default."""
 
     def __init__(self, reg_max, use_dfl, scalars):
+        self._scalars = scalars
         self.reg_max, self.use_dfl = reg_max, use_dfl
         self.nwd_loss = False
         self.iou_ratio = 0.5
         self.use_wiseiou = False
         self.wiou_loss = _WiouState(scalars)
+        self.iou_type = "CIoU"
+        self.iou_variant = None
+        self.inner_ratio, self.focaler_d, self.focaler_u, self.shape_scale, self.piou_lambda = 0.7, 0.0, 0.95, 0.0, 1.3
+
+    def __setattr__(self, name, value):
+        import math
+        from .metrics import WiseIouLoss
+        if name == "wiou_loss":
+            if isinstance(value, WiseIouLoss):
+                # a fresh object restarts the running mean, as constructing one in the reference does (its buffer starts at 1)
+                mean = float(value.iou_mean)
+                value._s = self._scalars
+                value.iou_mean = mean
+            elif not isinstance(value, _WiouState):
+                raise ValueError(f"bbox_loss.wiou_loss must be a WiseIouLoss, not {type(value).__name__}")
+        elif name == "iou_type" and value not in IOU_TYPES:
+            raise ValueError(f"iou_type={value!r}: must be one of {IOU_TYPES}")
+        elif name == "iou_variant" and value not in IOU_VARIANTS:
+            raise ValueError(f"iou_variant={value!r}: must be one of {IOU_VARIANTS}")
+        elif name in ("inner_ratio", "focaler_d", "focaler_u", "shape_scale", "piou_lambda"):
+            if not isinstance(value, (int, float)) or not math.isfinite(value) or (name == "inner_ratio" and value <= 0):
+                raise ValueError(f"{name}={value!r}: must be a finite number" + (" > 0" if name == "inner_ratio" else ""))
+            value = float(value)
+        object.__setattr__(self, name, value)
+
+    def configure_from_cfg(self, a):
+        """Apply the cfg keys iou_type / iou_variant / wiou_ltype / wiou_monotonous / wiou_inner / wiou_focaler (default.yaml)."""
+        from .metrics import WiseIouLoss
+        self.iou_type = getattr(a, "iou_type", None) or "CIoU"
+        self.iou_variant = getattr(a, "iou_variant", None) or None
+        if self.use_wiseiou:
+            try:
+                self.wiou_loss = WiseIouLoss(getattr(a, "wiou_ltype", None) or "WIoU", getattr(a, "wiou_monotonous", False),
+                                             bool(getattr(a, "wiou_inner", False)), bool(getattr(a, "wiou_focaler", False)))
+            except AssertionError as e:
+                raise ValueError(f"wiou_ltype: {e}") from None
+
+    def mode_fields(self):
+        """(box_family, box_ltype, box_fm, box_modifier, inner_ratio, focaler_d, focaler_u, shape_scale, piou_lambda) of
+        DyLossArgs.  All zero when the configuration is one of the legacy modes (CIoU or WIoU v3, plain)."""
+        from .metrics import WiseIouLoss
+        fam = lt = fm = mod = 0
+        if self.use_wiseiou:
+            w = self.wiou_loss
+            if isinstance(w, WiseIouLoss):
+                fm = 3 if w.monotonous is False else (2 if w.monotonous is True else 1)
+                mod = 1 if w.inner_iou else (2 if w.focaler_iou else 0)
+                if (w.ltype, fm, mod) != ("WIoU", 3, 0):
+                    fam, lt = 1, _LTYPE[w.ltype]
+        elif (self.iou_type, self.iou_variant) != ("CIoU", None):
+            fam, lt, mod = 2, _LTYPE[self.iou_type], IOU_VARIANTS.index(self.iou_variant)
+        if fam == 0:
+            return (0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0)
+        if mod == 2 and self.focaler_u == self.focaler_d:
+            raise ValueError(f"focaler_u == focaler_d == {self.focaler_u}: the Focaler interval is empty")
+        return (fam, lt, fm if fam == 1 else 0, mod, self.inner_ratio, self.focaler_d, self.focaler_u, self.shape_scale, self.piou_lambda)
 
 
 class v8DetectionLoss:
@@ -138,6 +208,8 @@ class v8DetectionLoss:
         a, b = self._args, self.bbox_loss
         a.hyp_box, a.hyp_cls, a.hyp_dfl = self.box_gain, self.cls_gain, self.dfl_gain
         a.use_wiou, a.use_nwd, a.iou_ratio = int(b.use_wiseiou), int(b.nwd_loss), float(b.iou_ratio)
+        (a.box_family, a.box_ltype, a.box_fm, a.box_modifier, a.inner_ratio, a.focaler_d, a.focaler_u, a.shape_scale,
+         a.piou_lambda) = b.mode_fields()
 
     @staticmethod
     def capacity_for(batch, B):

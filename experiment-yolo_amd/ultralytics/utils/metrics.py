@@ -141,3 +141,47 @@ class DetMetrics:
     @property
     def results_dict(self):
         return dict(zip(self.keys + ["fitness"], [*self.box.mean_results(), self.fitness]))
+
+
+class WiseIouLoss:
+    """Configuration of the Wise-IoU box loss (reference utils/metrics.py:567-741): ``ltype``, ``monotonous`` (None = v1, True =
+    v2, False = v3), ``inner_iou``, ``focaler_iou`` and the running mean ``iou_mean`` (starts at 1).  Assign it to
+    ``criterion.bbox_loss.wiou_loss`` with ``bbox_loss.use_wiseiou = True``; the loss itself runs in the criterion's HIP kernels
+    (``dy_detection_loss``), so the object is not called on tensors."""
+    momentum = 1e-2
+    alpha = 1.7
+    delta = 2.7
+    LTYPES = ("IoU", "WIoU", "EIoU", "GIoU", "DIoU", "CIoU", "SIoU", "ShapeIoU", "PIoU", "PIoU2", "MPDIoU")
+
+    def __init__(self, ltype="WIoU", monotonous=False, inner_iou=False, focaler_iou=False):
+        assert ltype in self.LTYPES, f"The loss function {ltype} does not exist"
+        self.ltype = ltype
+        self.monotonous = monotonous
+        self.inner_iou = inner_iou
+        self.focaler_iou = focaler_iou
+        self._s = None  # the criterion's scalar block once assigned to bbox_loss.wiou_loss (utils/loss.py BboxLoss)
+        self._mean = torch.tensor(1.0)
+        self.training = True
+
+    @property
+    def iou_mean(self):
+        """The running mean of the IoU term: the criterion's device scalar once assigned, else this object's own value."""
+        return self._s[4] if self._s is not None else self._mean
+
+    @iou_mean.setter
+    def iou_mean(self, v):
+        if self._s is not None:
+            self._s[4] = float(v)
+        else:
+            self._mean = torch.tensor(float(v))
+
+    def __call__(self, *args, **kwargs):
+        raise NotImplementedError("WiseIouLoss runs inside the detection criterion's HIP kernels: assign it to "
+                                  "v8DetectionLoss.bbox_loss.wiou_loss and call the criterion")
+
+    forward = __call__
+
+    def __repr__(self):
+        return f"{self.ltype}(iou_mean={float(self.iou_mean):.3f})"
+
+    __name__ = property(lambda self: self.ltype)

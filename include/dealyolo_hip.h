@@ -349,7 +349,41 @@ typedef struct DyLossArgs {
   const float* box_b[4];
   const float* box_in_coef[4];   /* NULL, or the BatchNorm coefficient table [4][64] of the Conv that produced box_in when box_in is that
                                     Conv's RAW output (no apply launch ran): BatchNorm + SiLU are applied where the rows are read */
+  /* ---- extended box loss (abi v2).  All zero: the four legacy modes above (use_wiou / use_nwd), unchanged. ---- */
+  int box_family;                /* DY_BOX_FAMILY_*: 0 legacy, 1 WiseIouLoss, 2 bbox_iou family; non-zero overrides use_wiou */
+  int box_ltype;                 /* DY_BOX_* loss type */
+  int box_fm;                    /* DY_BOX_FM_*: Wise focusing mechanism (family 1 only) */
+  int box_modifier;              /* DY_BOX_MOD_*: the plain, Inner or Focaler IoU term */
+  float inner_ratio;             /* get_inner_iou ratio, utils/metrics.py:186 (call sites: 0.7, utils/loss.py:207,213) */
+  float focaler_d, focaler_u;    /* Focaler-IoU interval, utils/metrics.py:375,618 (call sites: 0.0, 0.95) */
+  float shape_scale;             /* ShapeIoU scale, utils/metrics.py:153,685 (call site: 0.0, utils/loss.py:208) */
+  float piou_lambda;             /* PIoU2 Lambda, utils/metrics.py:179,722 (default 1.3) */
 } DyLossArgs;
+/* box_family codes */
+#define DY_BOX_FAMILY_LEGACY 0 /* BboxLoss.forward as shipped, utils/loss.py:206-218: CIoU or WIoU v3 per use_wiou */
+#define DY_BOX_FAMILY_WISE 1   /* WiseIouLoss(ltype, monotonous, inner_iou, focaler_iou), utils/metrics.py:567-741, utils/loss.py:207-210 */
+#define DY_BOX_FAMILY_BBOX 2   /* (1 - bbox_*iou(...)) * weight, utils/metrics.py:75-538, utils/loss.py:212-218 */
+/* box_ltype codes: WiseIouLoss._<ltype> (family 1) / the bbox_iou flag or bbox_*mpdiou (family 2) */
+#define DY_BOX_IOU 0      /* _IoU metrics.py:640 | bbox_iou() metrics.py:184 */
+#define DY_BOX_WIOU 1     /* _WIoU metrics.py:643 (family 1 only) */
+#define DY_BOX_EIOU 2     /* _EIoU metrics.py:647 | EIoU=True metrics.py:127-132 */
+#define DY_BOX_GIOU 3     /* _GIoU metrics.py:652 | GIoU=True metrics.py:182-183 */
+#define DY_BOX_DIOU 4     /* _DIoU metrics.py:655 | DIoU=True metrics.py:181 */
+#define DY_BOX_CIOU 5     /* _CIoU metrics.py:658 | CIoU=True metrics.py:122-126 */
+#define DY_BOX_SIOU 6     /* _SIoU metrics.py:665 | SIoU=True metrics.py:133-150 */
+#define DY_BOX_SHAPEIOU 7 /* _ShapeIoU metrics.py:685 | ShapeIoU=True metrics.py:151-167 */
+#define DY_BOX_PIOU 8     /* _PIoU metrics.py:708 | PIoU=True metrics.py:168-176 */
+#define DY_BOX_PIOU2 9    /* _PIoU2 metrics.py:722 | PIoU2=True metrics.py:177-180 */
+#define DY_BOX_MPDIOU 10  /* _MPDIoU metrics.py:680 | bbox_mpdiou / bbox_inner_mpdiou / bbox_focaler_mpdiou metrics.py:446-538;
+                             mpdiou_hw = (img_h^2 + img_w^2) / stride^2 per level, utils/loss.py:445 */
+/* box_fm codes (WiseIouLoss monotonous, metrics.py:568-572, _scaled_loss metrics.py:629-638) */
+#define DY_BOX_FM_V1 1 /* monotonous=None: no focusing */
+#define DY_BOX_FM_V2 2 /* monotonous=True: loss * sqrt(beta) */
+#define DY_BOX_FM_V3 3 /* monotonous=False: loss * beta / (delta * alpha^(beta - delta)) */
+/* box_modifier codes */
+#define DY_BOX_MOD_PLAIN 0   /* inter / union */
+#define DY_BOX_MOD_INNER 1   /* get_inner_iou metrics.py:186-218 (bbox_inner_iou metrics.py:220, inner_iou=True metrics.py:618) */
+#define DY_BOX_MOD_FOCALER 2 /* clamp((iou - d) / (u - d), 0, 1) (bbox_focaler_iou metrics.py:333, focaler_iou=True metrics.py:618) */
 int dy_loss_args_bytes(void); /* sizeof(DyLossArgs) in the library: bindings compare it with their own layout */
 size_t dy_loss_workspace_bytes(int B, int A, int nmax);
 /* byte offsets of pred_box (B,A,4 f32, grid units), assigned gt index (B,A i32, -1 = background) and target score
