@@ -147,6 +147,8 @@ static __device__ __forceinline__ half8 bn_bwd_apply8(const half8& dv, const hal
   return out;
 }
 
+#define DY_NUM_CUS 256  // MI355X: persistent grids are sized from this, never from the host
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 #define DY_CHECK_LAUNCH()                                  \

@@ -7,7 +7,9 @@
 // up holding 4*MT *contiguous* output channels of one pixel and stores them with one or two 16-byte writes.
 #include "common.h"
 #include "dealyolo_hip.h"
+#include "conv1x1_stream.h"
 #include <stdlib.h>
+#include <string.h>
 #include <stdio.h>
 #include <type_traits>
 
@@ -1822,7 +1824,6 @@ __global__ __launch_bounds__(512) void conv_mfma_dg2_kernel(ConvArgs a, int ntil
 }
 
 // ---- v4 (ping-pong) host side
-#define DY_NUM_CUS 256  // MI355X
 static bool g_force_v3 = getenv("DY_CONV_V3") != nullptr;
 static size_t pp_lds_bytes(int cc, int mt, int ks, int stride, int nch, int trows, int fw = 0) {
   const bool flat = ks == 1;
@@ -1843,6 +1844,65 @@ static int pp_trows(int cc, int mt, int ks, int stride, int nch) {
   if (!force1 && !(ks == 3 && stride == 2) && pp_lds_bytes(cc, mt, ks, stride, nch, 2) <= DY_WLDS_BUDGET) return 2;
   return pp_lds_bytes(cc, mt, ks, stride, nch, 1) <= DY_WLDS_BUDGET ? 1 : 0;
 }
+// ---- the streaming 1x1 kernel (conv1x1_stream.hip) or the ping-pong kernel's 1x1 branch?
+// DY_CONV1X1_STREAM: 0 = never, force = every launch the kernel supports whatever its size (the tests reach it on small shapes that
+// way), unset = the rule below.
+#define DY_STREAM_MIN_PIX 8192  // smallest launch the unset rule gives the stream kernel (between the measured tie at 6400 and win at 25600)
+static int conv1x1_stream_mode() {
+  static const int mode = [] {
+    const char* e = getenv("DY_CONV1X1_STREAM");
+    if (!e) return 1;
+    if (!strcmp(e, "0")) return 0;
+    return !strcmp(e, "force") ? 2 : 1;
+  }();
+  return mode;
+}
+// k-steps of 32 and the cout-group width the stream kernel would run this layer with (the geometry the weights are packed for); false:
+// the weights do not fit its register plan (more than DY_STREAM_MAX_KSTEPS k-steps, or 8-channel chunks)
+static bool conv1x1_stream_shape(int cin, int cout, int* nks, int* mt, int* ngroups, int* cpk) {
+  int cp, op, cc, nch, m, ng, kst, pe;
+  if (dy_conv_geometry(cin, cout, 1, 1, &cp, &op, &cc, &nch, &m, &ng, &kst, &pe) != DY_OK || cin != cp || cc < 16) return false;
+  *nks = nch * kst;
+  *mt = m;
+  *ngroups = ng;
+  *cpk = cc < 32 ? cc : 32;
+  return conv1x1_stream_has(*nks, m) != 0;
+}
+static bool segs_valid(const DySegs* s, int total);
+static int segs_chunk(int cin, int cout, const DySegs* s);
+// the Cin chunk the ping-pong kernel would stage this launch with (0: none)
+static int conv1x1_pp_chunk(int cin, int cout, const DySegs* xs) {
+  if (xs) return segs_chunk(cin, cout, xs);
+  int cp, op, cc, nch, m, ng, kst, pe;
+  return dy_conv_geometry(cin, cout, 1, 1, &cp, &op, &cc, &nch, &m, &ng, &kst, &pe) == DY_OK ? cc : 0;
+}
+// Does this 1x1 launch take the stream kernel?  Supported: fp16 store, DY_EPI_ACCUM, DY_EPI_STATS | DY_EPI_STATS_ACC; plain or segmented
+// input (whatever dy_conv1x1_segs_supported accepts, up-sampled members below 2^24 pixels); plain or segmented output.  Everything else
+// -- partial-row statistics, fp32 output, bias / SiLU / residual epilogues -- stays with the ping-pong kernel.
+static bool conv1x1_stream_wanted(int cin, int cout, int npix, int epi, const DySegs* xs, const DySegs* ys) {
+  const int mode = conv1x1_stream_mode();
+  if (!mode || npix <= 0) return false;
+  int nks, mt, ng, cpk;
+  if (!conv1x1_stream_shape(cin, cout, &nks, &mt, &ng, &cpk) || cout % 8) return false;
+  if (!(epi == 0 || epi == DY_EPI_ACCUM || epi == (DY_EPI_STATS | DY_EPI_STATS_ACC))) return false;
+  if (xs) {
+    if (!segs_valid(xs, cin) || !segs_chunk(cin, cout, xs)) return false;
+    for (int k = 0; k < xs->nseg; ++k)
+      if ((xs->acc[k] & 2) && npix >= (1 << 24)) return false;
+  }
+  if (ys && (epi || !segs_valid(ys, cout))) return false;
+  if (epi & DY_EPI_STATS) {  // the sums are taken on the ping-pong kernel's 256-pixel tiles (conv1x1_stream_kernel, PP): it must be the
+    const int c = conv1x1_pp_chunk(cin, cout, xs);  // kernel this launch would otherwise run, with 64 pixels per wave
+    if (!c || cin % c || pp_trows(c, mt, 1, 1, cin / c) != 2) return false;
+  }
+  if (mode == 2) return true;
+  // The rule (per-shape table of profiles/r05_conv1x1_stream.md): at batch 64 the stream kernel wins on every map (160x160
+  // -9 %, 80x80 -22...-43 %, 40x40 -10...-26 %, 20x20 = 25600 pixels -14 %).  From 400 to 6400 pixels both kernels sit on the ~8 us launch
+  // floor: the 32- and 64-channel shapes tie within the +-0.3 us repeat noise (the 128-channel ones gain 1.5-2 us), nothing a step could
+  // show.  Launches that small keep the ping-pong kernel.
+  return npix >= DY_STREAM_MIN_PIX;
+}
+
 // workgroups of a ping-pong launch: every workgroup resident at once (one per CU, two when two fit in LDS), each owning
 // two tiles per period; this is also the number of BN partial rows the launch writes
 static int pp_grid(int cc, int mt, int ks, int stride, int nch, int trows, int ntiles, int fw = 0) {
@@ -2146,6 +2206,22 @@ static int conv_forward_impl(const void* x, int ldx, const void* w_packed, const
     DY_DG2(32, 1) DY_DG2(32, 2) DY_DG2(32, 4) DY_DG2(64, 1) DY_DG2(64, 2) DY_DG2(64, 4)
 #undef DY_DG2
   }
+  if (ks == 1 && !(red && (red->raw || red->res)) && !(ldy & 7) && !((uintptr_t)y & 15) &&
+      conv1x1_stream_wanted(cin, cout, a.npix, epi, segx ? red->xs : nullptr, segy ? red->ys : nullptr)) {
+    Conv1x1StreamArgs sa{};
+    int nks, smt, sng, cpk;
+    if (!conv1x1_stream_shape(cin, cout, &nks, &smt, &sng, &cpk)) return DY_ERR_ARG;
+    sa.w = a.w; sa.y = y; sa.acc = reinterpret_cast<double*>(partials); sa.ldy = ldy; sa.npix = a.npix; sa.cout = cout; sa.epi = epi;
+    sa.cpk = cpk; sa.N = n; sa.H = h; sa.W = w;
+    if (segx) {
+      sa.xs = *red->xs;
+    } else {  // a plain tensor is one segment
+      sa.xs.nseg = 1; sa.xs.c_end[0] = cin; sa.xs.ld[0] = ldx; sa.xs.acc[0] = 0; sa.xs.ptr[0] = x;
+    }
+    if (segy) sa.ys = *red->ys;
+    if (epi & DY_EPI_STATS) sa.pp_grid = pp_grid(cc, mt, 1, 1, nch, 2, cdiv(a.npix, 256));  // cc, nch: what the ping-pong launch would use
+    return conv1x1_stream_launch(sa, nks, smt, sng, stream);
+  }
   if (ks == 1) return dispatch_cc_mt<1, 1, 2>(cc, mt, a, gx, ng, stream);
   if (stride == 1) return dispatch_cc_mt<3, 1, 2>(cc, mt, a, gx, ng, stream);
   return dispatch_cc_mt<3, 2, 1>(cc, mt, a, gx, ng, stream);
@@ -2167,6 +2243,23 @@ extern "C" int dy_conv_kernel_name(int cin, int cout, int ks, int stride, char* 
   else if (cfg == 1) snprintf(out, cap, "conv_mfma_wlds_kernel<%d, %d, %d, %d, 1, 8>", cc, mt, ks, stride);
   else snprintf(out, cap, "conv_mfma_kernel<%d, %d, %d, %d, %d>", cc, mt, ks, stride, (ks == 3 && stride == 2) ? 1 : 2);
   return DY_OK;
+}
+
+// name of the kernel a 1x1 launch REALLY runs (dy_conv_forward with ks = 1, dy_conv1x1_forward_segs with xs, dy_conv1x1_input_grad_segs
+// with ys): the stream kernel where conv1x1_stream_wanted selects it, else the ping-pong instantiation the helpers above name.
+// It sees the geometry, not the pointers: an output with ldy % 8 != 0 or a y that is not 16-byte aligned (legal for the ping-pong
+// kernel, never produced by the engine) also keeps a launch on the ping-pong kernel, and this function cannot know.
+extern "C" int dy_conv1x1_kernel_name_live(int cin, int cout, int n, int h, int w, int epi, const DySegs* xs, const DySegs* ys, char* out,
+                                           int cap) {
+  if (!out || cap < 8) return DY_ERR_ARG;
+  if ((double)n * h * w < 2147483648.0 && conv1x1_stream_wanted(cin, cout, n * h * w, epi, xs, ys)) {
+    int nks, mt, ng, cpk;
+    if (!conv1x1_stream_shape(cin, cout, &nks, &mt, &ng, &cpk)) return DY_ERR_ARG;
+    snprintf(out, cap, "conv1x1_stream_kernel<%d, %d, %s>", nks, mt, (epi & DY_EPI_STATS) ? "true" : "false");
+    return DY_OK;
+  }
+  if (xs) return dy_conv1x1_segs_kernel_name(cin, cout, xs, out, cap);
+  return dy_conv_kernel_name(cin, cout, 1, 1, out, cap);
 }
 
 // ... for a given output width and epilogue: maps exactly 40 (80) pixels wide take the full-width tiles of conv_mfma_pp_kernel (last

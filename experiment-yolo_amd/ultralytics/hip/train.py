@@ -757,16 +757,18 @@ class StepPlan:
             if dil == 2 and ks == 3:
                 return f"conv_mfma_dg2_kernel (input gradient of the {cout}->{cin} stride-2 3x3)", self.conv_algorithmic_bytes(args)
             pad = ks // 2
+            if ks == 1 and L.dy_conv1x1_kernel_name_live(cin, cout, n, h, w, int(args[17]), None, None, buf, 128) == 0:  # the launch really made
+                return buf.value.decode(), self.conv_algorithmic_bytes(args)
             if L.dy_conv_kernel_name_at(cin, cout, ks, stride, (w + 2 * pad - ks) // stride + 1, dil, int(args[17]), buf, 128) == 0:
                 return buf.value.decode(), self.conv_algorithmic_bytes(args)
         # 1x1 convolutions over a never-materialised concatenation (the segment table travels by reference: args[k]._obj)
         if name == "dy_conv1x1_forward_segs":
             n, h, w, cin, cout = args[6:11]
-            if L.dy_conv1x1_segs_kernel_name(cin, cout, args[0], buf, 128) == 0:
+            if L.dy_conv1x1_kernel_name_live(cin, cout, n, h, w, int(args[11]), args[0], None, buf, 128) == 0:
                 return buf.value.decode(), n * h * w * (cin + (cout + 7) // 8 * 8) * 2
         if name == "dy_conv1x1_input_grad_segs":  # (dy, lddy, w^T, dxs, n, h, w, channels of dy, channels of the concatenation)
             n, h, w, cin, cout = args[4:9]
-            if L.dy_conv_kernel_name(cin, cout, 1, 1, buf, 128) == 0:
+            if L.dy_conv1x1_kernel_name_live(cin, cout, n, h, w, 0, None, args[3], buf, 128) == 0:
                 return buf.value.decode(), n * h * w * (cin + cout) * 2
         if name in ("dy_conv1x1_wgrad_bn_segs", "dy_conv1x1_wgrad_bn_planes"):
             n, h, w, cin, cout = args[13:18] if name.endswith("segs") else args[17:22]

@@ -135,6 +135,14 @@ int dy_conv_wgrad_ld_bn(const void* x, int ldx, const void* dy, int lddy, const 
  * cuts (the geometry's own, or 32 where that is 64: same packed weights) and the ping-pong kernel takes the shape. */
 int dy_conv1x1_segs_supported(int cin, int cout, const DySegs* xs);
 int dy_conv1x1_segs_kernel_name(int cin, int cout, const DySegs* xs, char* out, int cap); /* as dy_conv_kernel_name, for dy_conv1x1_forward_segs */
+/* host-side: the kernel a 1x1 launch really runs, spelled as rocprofv3 prints it -- Conv.forward of a k = 1 Conv (nn/modules/conv.py:49-55)
+ * or its input gradient through dy_conv_forward (xs = ys = NULL), dy_conv1x1_forward_segs (xs) or dy_conv1x1_input_grad_segs (ys: cin =
+ * channels of dy, cout = channels of the concatenation, epi 0).  conv1x1_stream_kernel<k-steps, MT, PP> (csrc/conv1x1_stream.hip; PP = true for launches with BatchNorm sums) where the
+ * selection rule takes it -- fp16 store, DY_EPI_ACCUM or DY_EPI_STATS | DY_EPI_STATS_ACC, Cin <= 128; environment DY_CONV1X1_STREAM:
+ * 0 = never, force = every supported launch, unset = the measured rule -- else what dy_conv_kernel_name / dy_conv1x1_segs_kernel_name
+ * return, which keep naming the ping-pong instantiation of the geometry.  Decided from the geometry alone: an output whose pixel stride
+ * is not a multiple of 8 or whose base is not 16-byte aligned also stays on the ping-pong kernel, which this function cannot see. */
+int dy_conv1x1_kernel_name_live(int cin, int cout, int n, int h, int w, int epi, const DySegs* xs, const DySegs* ys, char* out, int cap);
 int dy_conv1x1_forward_segs(const DySegs* xs, const void* w_packed, const float* bias, void* y, int ldy, float* partials, int n, int h,
                             int w, int cin, int cout, int epi, hipStream_t stream);
 int dy_conv1x1_input_grad_segs(const void* dy, int lddy, const void* w_packed_t, const DySegs* dxs, int n, int h, int w, int cin, int cout,

@@ -27,11 +27,13 @@ Ho, Wo = eng.out_hw(sp, xa)
 y = Storage(eng, N, Ho, Wo, (cout + 7) // 8 * 8)
 y.buf.copy_(torch.randn_like(y.buf))
 ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+EPI = int(os.environ.get("DY_EPI", "0"))  # 16 = accumulate, 33 = BatchNorm sums into an fp64 accumulator (DY_EPI_STATS | DY_EPI_STATS_ACC)
+ACC = torch.zeros(16 * 2 * ((cout + 15) // 16 * 16), dtype=torch.float64, device="cuda")
 
 
 def run():
     if mode == "fwd":
-        eng._conv_raw(sp, xa, y.buf.data_ptr(), y.C, int(os.environ.get("DY_EPI", "0")))
+        eng._conv_raw(sp, xa, y.buf.data_ptr(), y.C, EPI, ACC.data_ptr() if EPI & 1 else 0)
     else:
         eng._conv_bwd(sp, Storage.act(x) if False else xa, y.buf.data_ptr(), y.C, Ho, Wo)
 
