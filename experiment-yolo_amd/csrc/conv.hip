@@ -1431,51 +1431,70 @@ __global__ __launch_bounds__(256) void pack_weights_batched_kernel(const PackDes
 }
 
 // ----------------------------------------------------------------------------------------------------------------
-static int pp_trows(int cc, int mt, int ks, int stride, int nch);
-static int pick_cc(int cin_p, int ks, int stride) {
-  static const int forced = getenv("DY_CONV_CC") ? atoi(getenv("DY_CONV_CC")) : 0;  // measurement switch, read once
-  if (forced && cin_p % forced == 0) return forced;
-  // 64-channel stride-2 3x3: 16-channel chunks.  A stride-2 halo tile is 9 x 65 pixels for 4 x 32 outputs, so the staged bytes per MFMA
-  // are four times a stride-1 tile's; with 32-channel chunks the tile + weights only fit for 32-wide cout groups, i.e. 64->128 staged
-  // its input four times.  16-channel chunks leave room for the 64-wide group: 78.1 -> 61.0 us (64->128 @80x80), 43.1 -> 32.7 (64->64);
-  // narrower inputs lose with them (32->64 @160: 36.4 -> 44.2), gpurun_out/s2_sweep.log.
-  if (ks == 3 && stride == 2 && cin_p == 64) return 16;
-  const int cap = (ks == 3 && stride == 2) ? 32 : 64;
-  if (cin_p <= cap && (cin_p == 8 || cin_p == 16 || cin_p == 32 || cin_p == 64)) return cin_p;
-  if (cin_p % 64 == 0 && cap >= 64) return 64;
-  if (cin_p % 32 == 0) return 32;
-  if (cin_p % 16 == 0) return 16;
-  return 8;
+// Host side.  conv_geom() fixes how a layer's weights are packed; conv_plan() (below the dg2 kernel) decides everything about one
+// launch -- kernel family, template arguments, tiles, grid, LDS -- and every entry point and planning helper reads its answer.
+#define DY_WLDS_BUDGET (156 * 1024)
+#define DY_WLDS_MAX_WGS 512
+static bool g_force_v1 = getenv("DY_CONV_V1") != nullptr;
+
+// LDS bytes of the ping-pong kernel with `trows` output rows per wave (1x1: 32*trows pixels per wave); fw: full-width tiles
+static size_t pp_lds_bytes(int cc, int mt, int ks, int stride, int nch, int trows, int fw = 0) {
+  const bool flat = ks == 1;
+  const bool swz = ks == 3 && stride == 1 && cc == 32;  // conv_mfma_pp_kernel, SWZ: 64-byte pixels, rows padded to a multiple of 8 pixels
+  const int th = 4 * trows, hw = flat ? 4 * 2 * trows * 16 : (swz ? ((fw ? fw : 32) + 2 + 7) / 8 * 8 : 31 * stride + ks), hh = flat ? 1 : (th - 1) * stride + ks;
+  size_t tile = (size_t)hh * hw * (swz ? 64 : ps_bytes(cc, stride));
+  const size_t red = 8 * 2 * 16 * mt * 4;
+  if (tile < red) tile = red;
+  const size_t wts = (size_t)nch * ((ks * ks * cc + 31) / 32) * 16 * mt * 64;
+  const size_t xpose = 8 * 16 * (size_t)(32 * mt + 16);  // per-wave store-transpose scratch
+  return 2 * tile + wts + xpose + 3 * 16 * mt * 4 + (flat ? 256 : 0);  // + this cout group's bias + the RED coefficient table (scale | shift)
+                                                                        // + (1x1) the per-chunk table of a segmented input
 }
-// cout rows per workgroup = 16*MT.  48 / 80 / 96-channel outputs take MT = 4 with a padded last group (zero weight rows, masked
-// stores): these layers are memory-bound, and MT = 1 would stream the whole input once per 16 output channels
-static int pick_mt(int cout16) {
-  static const int forced = getenv("DY_CONV_MT") ? atoi(getenv("DY_CONV_MT")) : 0;  // measurement switch, read once
-  if (forced) return forced;
-  return cout16 >= 48 ? 4 : (cout16 == 32 ? 2 : 1);
+// rows per wave of the ping-pong kernel for a chunking (0 = does not fit: v3 / v1 take it)
+static int pp_trows(int cc, int mt, int ks, int stride, int nch) {
+  if (g_force_v1 || (cc == 64 && stride == 2)) return 0;
+  if (!(ks == 3 && stride == 2) && pp_lds_bytes(cc, mt, ks, stride, nch, 2) <= DY_WLDS_BUDGET) return 2;
+  return pp_lds_bytes(cc, mt, ks, stride, nch, 1) <= DY_WLDS_BUDGET ? 1 : 0;
+}
+// LDS bytes of the v3 kernel (8 waves) with `trows` output rows per wave (1x1: 32*trows pixels per wave)
+static size_t wlds_bytes_t(int cc, int mt, int ks, int stride, int nch, int trows) {
+  const bool flat = ks == 1;
+  const int nw = 8, th = nw * trows, hw = flat ? nw * 2 * trows * 16 : 31 * stride + ks, hh = flat ? 1 : (th - 1) * stride + ks;
+  size_t tile = (size_t)hh * hw * ps_bytes(cc, stride);
+  const size_t red = nw * 2 * 16 * mt * 4;
+  if (tile < red) tile = red;
+  const size_t wts = (size_t)nch * ((ks * ks * cc + 31) / 32) * 16 * mt * 64;
+  return tile + wts;
+}
+// rows per wave of the v3 kernel for a chunking (0 = not applicable: v1 takes it)
+static int v3_trows(int cc, int mt, int ks, int stride, int nch) {
+  if (g_force_v1 || (cc == 64 && stride == 2)) return 0;
+  if (!(ks == 3 && stride == 2) && wlds_bytes_t(cc, mt, ks, stride, nch, 2) <= DY_WLDS_BUDGET) return 2;
+  return wlds_bytes_t(cc, mt, ks, stride, nch, 1) <= DY_WLDS_BUDGET ? 1 : 0;
 }
 
-extern "C" int dy_conv_geometry(int cin, int cout, int ks, int stride, int* cin_p, int* cout_p, int* cc, int* nch,
-                                int* mt, int* ngroups, int* ksteps, int* packed_elems) {
-  if (!(ks == 1 || ks == 3) || !(stride == 1 || stride == 2) || (ks == 1 && stride != 1)) return DY_ERR_ARG;
+struct ConvGeom { int rc, cin_p, cout_p, cc, nch, mt, ngroups, ksteps, packed_elems; };
+static ConvGeom conv_geom(int cin, int cout, int ks, int stride) {
+  ConvGeom g{};
+  g.rc = DY_ERR_ARG;
+  if (!(ks == 1 || ks == 3) || !(stride == 1 || stride == 2) || (ks == 1 && stride != 1)) return g;
   const int cp = (cin + 7) / 8 * 8, op = (cout + 15) / 16 * 16;
-  int c = pick_cc(cp, ks, stride);
-  int m = pick_mt(op);
-  static const bool cc64 = getenv("DY_CONV_CC64") != nullptr;  // measurement switch, read once
-  // 64-channel 3x3 with a 64-wide cout group: two 32-channel chunks let the 16-row halo tile share LDS with the 72 KiB
-  // of weights, so each wave owns 64 pixels (4 N-tiles) and re-reads half as many A fragments per MFMA
-  if (ks == 3 && stride == 1 && c == 64 && m == 4 && !cc64) c = 32;
-  // Prefer a shape the weights-in-LDS ping-pong kernel can take: wide layers (128+ channels: 3x3 weights of a 64-wide cout
-  // group are 147+ KB) narrow the cout group to 32 or 16 rows and, for 3x3, the Cin chunk to 32.  The input is then
-  // streamed once per cout group, but these layers sit at 40x40 / 20x20 where the whole activation tensor is L2/MALL
-  // resident; the alternative (v1 kernel, A fragments from L2) measured 150-300 TFLOP/s on them.
-  // (Only up to 128x128 channels: beyond, the cout groups multiply while the 20x20 maps leave each workgroup a handful of
-  // tiles per 74 KB weight load -- 256->256 @20x20 and 128->256 s2 measured 15-55 % slower this way.)
-  // Stride-2 3x3 over 128 input channels (yolov8n-p2's 128->256 / 128->128 down-sampling convs at 80x80): the halo tile of a stride-2
-  // kernel is four times a stride-1 tile's, so only 16-channel chunks leave room for a 32-wide cout group beside it -- without them
-  // 128->128 ran on 16-wide groups (input staged eight times, 84 TFLOP/s) and 128->256 on the v1 kernel (A fragments from L2).
-  static const bool s2cc16 = getenv("DY_CONV_S2_CC16") == nullptr || atoi(getenv("DY_CONV_S2_CC16")) != 0;
-  const bool s2wide = s2cc16 && ks == 3 && stride == 2 && cp == 128 && op <= 128;  // (128->256 on 32-wide groups measured SLOWER than v1: 227 vs 174 us)
+  // Cin chunk (DESIGN 4.1 has the measurements behind every rule here).  Stride-2 3x3 tiles are four times a stride-1 tile's:
+  // 32-channel chunks at most, 16 over 64 input channels so that a 64-wide cout group fits beside the tile
+  const int cap = (ks == 3 && stride == 2) ? 32 : 64;
+  int c = 8;
+  if (ks == 3 && stride == 2 && cp == 64) c = 16;
+  else if (cp <= cap && (cp == 8 || cp == 16 || cp == 32 || cp == 64)) c = cp;
+  else if (cp % 64 == 0 && cap >= 64) c = 64;
+  else if (cp % 32 == 0) c = 32;
+  else if (cp % 16 == 0) c = 16;
+  // cout rows per workgroup = 16*MT; 48 / 80 / 96-channel outputs take MT = 4 with a padded last group (zero rows, masked stores)
+  int m = op >= 48 ? 4 : (op == 32 ? 2 : 1);
+  // 64-channel 3x3 with a 64-wide cout group: two 32-channel chunks, so that the 16-row halo tile fits beside the 72 KiB of weights
+  if (ks == 3 && stride == 1 && c == 64 && m == 4) c = 32;
+  // Prefer a shape the ping-pong kernel can take: layers of up to 128 x 128 channels (stride-2 3x3 over 128 input channels: up to 128
+  // outputs) narrow the cout group to 32 or 16 rows and the chunk to 32 (stride 2: 16) until the weights and two tiles fit in LDS
+  const bool s2wide = ks == 3 && stride == 2 && cp == 128 && op <= 128;
   if (pp_trows(c, m, ks, stride, cp / c) == 0 && cp <= 128 && (op <= 128 || s2wide)) {
     bool found = false;
     for (int mm = m; mm >= 1 && !found; mm >>= 1)
@@ -1488,120 +1507,66 @@ extern "C" int dy_conv_geometry(int cin, int cout, int ks, int stride, int* cin_
         }
       }
   }
-  *cin_p = cp;
-  *ngroups = (op + 16 * m - 1) / (16 * m);
-  *cout_p = *ngroups * 16 * m;
-  *cc = c;
-  *nch = cp / c;
-  *mt = m;
-  *ksteps = (ks * ks * c + 31) / 32;
-  *packed_elems = (*ngroups) * (*nch) * (*ksteps) * 16 * m * 32;
+  g.rc = DY_OK;
+  g.cin_p = cp;
+  g.ngroups = (op + 16 * m - 1) / (16 * m);
+  g.cout_p = g.ngroups * 16 * m;
+  g.cc = c;
+  g.nch = cp / c;
+  g.mt = m;
+  g.ksteps = (ks * ks * c + 31) / 32;
+  g.packed_elems = g.ngroups * g.nch * g.ksteps * 16 * m * 32;
+  return g;
+}
+extern "C" int dy_conv_geometry(int cin, int cout, int ks, int stride, int* cin_p, int* cout_p, int* cc, int* nch,
+                                int* mt, int* ngroups, int* ksteps, int* packed_elems) {
+  const ConvGeom g = conv_geom(cin, cout, ks, stride);
+  if (g.rc != DY_OK) return g.rc;
+  *cin_p = g.cin_p; *cout_p = g.cout_p; *cc = g.cc; *nch = g.nch;
+  *mt = g.mt; *ngroups = g.ngroups; *ksteps = g.ksteps; *packed_elems = g.packed_elems;
   return DY_OK;
 }
 
-extern "C" int dy_pack_weights_ld(const float* w, void* out, int cout, int cin, int ld_taps, int ld_cphys, int transposed,
-                                  hipStream_t stream) {
-  int cp, op, cc, nch, mt, ng, kst, pe;
-  const int keff = ld_taps * ld_cphys, coutp = (cout + 7) / 8 * 8;
-  const int pin = transposed ? coutp : keff, pout = transposed ? keff : cout;
-  if (dy_conv_geometry(pin, pout, 1, 1, &cp, &op, &cc, &nch, &mt, &ng, &kst, &pe) != DY_OK) return DY_ERR_ARG;
-  PackArgs a{w, nullptr, (f16*)out, cout, cin, 1, cc, nch, mt, ng, kst, transposed, ld_taps, ld_cphys};
-  const int blocks = cdiv(pe, 256) < 1024 ? cdiv(pe, 256) : 1024;
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, stream, a);
+// ---- weight packing (dealyolo_hip.h).  The geometry is that of the pass that will consume the pack: (cin -> cout) forward, (cout -> cin)
+// stride-1 dgrad when transposed, or (ld_taps > 0) the 1x1 over the ld_taps * ld_cphys gathered channels of an LDConv.  Returns the
+// packed elements, 0: unsupported.
+static int pack_plan(PackArgs* a, const float* w, const float* scale, void* out, int cout, int cin, int ks, int stride, int transposed,
+                     int ld_taps, int ld_cphys) {
+  if (ld_taps) ks = stride = 1;
+  const int fin = ld_taps ? ld_taps * ld_cphys : cin, fout = (ld_taps && transposed) ? (cout + 7) / 8 * 8 : cout;
+  const ConvGeom g = conv_geom(transposed ? fout : fin, transposed ? fin : fout, ks, transposed ? 1 : stride);
+  if (g.rc != DY_OK) return 0;
+  *a = PackArgs{w, scale, (f16*)out, cout, cin, ks, g.cc, g.nch, g.mt, g.ngroups, g.ksteps, transposed, ld_taps, ld_cphys};
+  return g.packed_elems;
+}
+static int pack_launch(const float* w, const float* scale, void* out, int cout, int cin, int ks, int stride, int transposed, int ld_taps,
+                       int ld_cphys, hipStream_t stream) {
+  PackArgs a;
+  const int pe = pack_plan(&a, w, scale, out, cout, cin, ks, stride, transposed, ld_taps, ld_cphys);
+  if (!pe) return DY_ERR_ARG;
+  hipLaunchKernelGGL(pack_weights_kernel, dim3(cdiv(pe, 256) < 1024 ? cdiv(pe, 256) : 1024), dim3(256), 0, stream, a);
   DY_CHECK_LAUNCH();
   return DY_OK;
 }
-
-// Fill one host-side descriptor (sizeof = dy_pack_desc_bytes()) for dy_pack_weights_batched; returns its block count.
+extern "C" int dy_pack_weights(const float* w, const float* scale, void* out, int cout, int cin, int ks, int stride,
+                               int transposed, hipStream_t stream) {
+  return pack_launch(w, scale, out, cout, cin, ks, stride, transposed, 0, 0, stream);
+}
+extern "C" int dy_pack_weights_ld(const float* w, void* out, int cout, int cin, int ld_taps, int ld_cphys, int transposed,
+                                  hipStream_t stream) {
+  return ld_taps > 0 ? pack_launch(w, nullptr, out, cout, cin, 1, 1, transposed, ld_taps, ld_cphys, stream) : DY_ERR_ARG;
+}
 extern "C" int dy_pack_desc_bytes(void) { return (int)sizeof(PackDesc); }
 extern "C" int dy_pack_desc_fill(void* desc, const float* w, const float* scale, void* out, int cout, int cin, int ks,
                                  int stride, int transposed, int ld_taps, int ld_cphys, int first_block) {
-  int cp, op, cc, nch, mt, ng, kst, pe;
-  int pin, pout;
-  if (ld_taps) {
-    const int keff = ld_taps * ld_cphys, coutp = (cout + 7) / 8 * 8;
-    pin = transposed ? coutp : keff;
-    pout = transposed ? keff : cout;
-    ks = 1;
-    stride = 1;
-  } else {
-    pin = transposed ? cout : cin;
-    pout = transposed ? cin : cout;
-  }
-  if (dy_conv_geometry(pin, pout, ks, transposed ? 1 : stride, &cp, &op, &cc, &nch, &mt, &ng, &kst, &pe) != DY_OK) return DY_ERR_ARG;
   PackDesc* d = reinterpret_cast<PackDesc*>(desc);
-  d->a = PackArgs{w, scale, (f16*)out, cout, cin, ks, cc, nch, mt, ng, kst, transposed, ld_taps, ld_cphys};
-  d->total = pe;
+  d->total = pack_plan(&d->a, w, scale, out, cout, cin, ks, stride, transposed, ld_taps, ld_cphys);
   d->first_block = first_block;
-  return cdiv(pe, 1024);
+  return d->total ? cdiv(d->total, 1024) : DY_ERR_ARG;
 }
 extern "C" int dy_pack_weights_batched(const void* descs_device, int n, int total_blocks, hipStream_t stream) {
   if (n <= 0 || total_blocks <= 0) return DY_ERR_ARG;
   hipLaunchKernelGGL(pack_weights_batched_kernel, dim3(total_blocks), dim3(256), 0, stream, (const PackDesc*)descs_device, n);
-  DY_CHECK_LAUNCH();
-  return DY_OK;
-}
-
-extern "C" int dy_pack_weights(const float* w, const float* scale, void* out, int cout, int cin, int ks, int stride,
-                               int transposed, hipStream_t stream) {
-  // geometry is that of the pass that will consume the pack: (cin -> cout) forward, or (cout -> cin) stride-1 dgrad
-  int cp, op, cc, nch, mt, ng, kst, pe;
-  const int pin = transposed ? cout : cin, pout = transposed ? cin : cout;
-  if (dy_conv_geometry(pin, pout, ks, transposed ? 1 : stride, &cp, &op, &cc, &nch, &mt, &ng, &kst, &pe) != DY_OK)
-    return DY_ERR_ARG;
-  PackArgs a{w, scale, (f16*)out, cout, cin, ks, cc, nch, mt, ng, kst, transposed, 0, 0};
-  const int blocks = cdiv(pe, 256) < 1024 ? cdiv(pe, 256) : 1024;
-  hipLaunchKernelGGL(pack_weights_kernel, dim3(blocks), dim3(256), 0, stream, a);
-  DY_CHECK_LAUNCH();
-  return DY_OK;
-}
-
-#define DY_WLDS_BUDGET (156 * 1024)
-#define DY_WLDS_MAX_WGS 512
-static bool g_force_v1 = getenv("DY_CONV_V1") != nullptr;
-
-// LDS bytes of the v3 kernel with `nw` waves and `trows` output rows per wave (FLAT: 32*trows pixels per wave)
-static size_t wlds_bytes_t(int cc, int mt, int ks, int stride, int nch, int trows, int nw = 8) {
-  const bool flat = ks == 1;
-  const int th = nw * trows, hw = flat ? nw * 2 * trows * 16 : 31 * stride + ks, hh = flat ? 1 : (th - 1) * stride + ks;
-  size_t tile = (size_t)hh * hw * ps_bytes(cc, stride);
-  const size_t red = nw * 2 * 16 * mt * 4;
-  if (tile < red) tile = red;
-  const size_t wts = (size_t)nch * ((ks * ks * cc + 31) / 32) * 16 * mt * 64;
-  return tile + wts;
-}
-// v3 configuration for a geometry: 2 = 8 waves x 2 rows (preferred), 4 = 4 waves x 2 rows (same per-wave tile, fits when the
-// 16-row halo does not: 64-channel 3x3), 1 = 8 waves x 1 row, 0 = v3 not applicable
-static bool g_no_nw4 = getenv("DY_CONV_NW4") == nullptr;  // measured slower (224 vs 202 us on 64->64 3x3 @160^2): opt-in only
-static int v3_trows(int cc, int mt, int ks, int stride, int nch) {
-  if (ks == 3 && stride == 2) return wlds_bytes_t(cc, mt, ks, stride, nch, 1) <= DY_WLDS_BUDGET ? 1 : 0;
-  if (wlds_bytes_t(cc, mt, ks, stride, nch, 2) <= DY_WLDS_BUDGET) return 2;
-  if (!g_no_nw4 && ks == 3 && wlds_bytes_t(cc, mt, ks, stride, nch, 2, 4) <= DY_WLDS_BUDGET) return 4;
-  return wlds_bytes_t(cc, mt, ks, stride, nch, 1) <= DY_WLDS_BUDGET ? 1 : 0;
-}
-static int v3_tile_rows(int cfg) { return cfg == 2 ? 16 : 8; }
-static int v3_flat_pix(int cfg) { return cfg == 2 ? 512 : (cfg == 4 ? 256 : 256); }
-
-
-template <int CC, int MT, int KS, int STRIDE, int TR3, int NW>
-static int launch_v3(const ConvArgs& a, int grid_y, hipStream_t s) {
-  static bool attr_set = false;
-  auto kern = conv_mfma_wlds_kernel<CC, MT, KS, STRIDE, TR3, NW>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, DY_WLDS_BUDGET) != hipSuccess)
-      return DY_ERR_LAUNCH;
-    attr_set = true;
-  }
-  ConvArgs b = a;
-  int ntiles;
-  if (KS == 1) {
-    ntiles = cdiv(a.npix, NW * 2 * TR3 * 16);
-  } else {
-    b.tiles_y = cdiv(a.Ho, NW * TR3);
-    ntiles = b.tiles_x * b.tiles_y * a.N;
-  }
-  const int gx = ntiles < DY_WLDS_MAX_WGS ? ntiles : DY_WLDS_MAX_WGS;
-  hipLaunchKernelGGL(kern, dim3(gx, grid_y), dim3(NW * 64), wlds_bytes_t(CC, MT, KS, STRIDE, a.nch, TR3, NW), s, b, ntiles);
   DY_CHECK_LAUNCH();
   return DY_OK;
 }
@@ -1823,86 +1788,18 @@ __global__ __launch_bounds__(512) void conv_mfma_dg2_kernel(ConvArgs a, int ntil
   }
 }
 
-// ---- v4 (ping-pong) host side
-static bool g_force_v3 = getenv("DY_CONV_V3") != nullptr;
-static size_t pp_lds_bytes(int cc, int mt, int ks, int stride, int nch, int trows, int fw = 0) {
-  const bool flat = ks == 1;
-  const bool swz = ks == 3 && stride == 1 && cc == 32;  // conv_mfma_pp_kernel, SWZ: 64-byte pixels, rows padded to a multiple of 8 pixels
-  const int th = 4 * trows, hw = flat ? 4 * 2 * trows * 16 : (swz ? ((fw ? fw : 32) + 2 + 7) / 8 * 8 : 31 * stride + ks), hh = flat ? 1 : (th - 1) * stride + ks;
-  size_t tile = (size_t)hh * hw * (swz ? 64 : ps_bytes(cc, stride));
-  const size_t red = 8 * 2 * 16 * mt * 4;
-  if (tile < red) tile = red;
-  const size_t wts = (size_t)nch * ((ks * ks * cc + 31) / 32) * 16 * mt * 64;
-  const size_t xpose = 8 * 16 * (size_t)(32 * mt + 16);  // per-wave store-transpose scratch
-  return 2 * tile + wts + xpose + 3 * 16 * mt * 4 + (flat ? 256 : 0);  // + this cout group's bias + the RED coefficient table (scale | shift)
-                                                                        // + (1x1) the per-chunk table of a segmented input
-}
-// rows per wave of the ping-pong kernel for a geometry (0 = does not fit: v3/v1 take it)
-static int pp_trows(int cc, int mt, int ks, int stride, int nch) {
-  if (g_force_v1 || g_force_v3 || (cc == 64 && stride == 2)) return 0;
-  static const bool force1 = getenv("DY_PP_TROWS1") != nullptr;
-  if (!force1 && !(ks == 3 && stride == 2) && pp_lds_bytes(cc, mt, ks, stride, nch, 2) <= DY_WLDS_BUDGET) return 2;
-  return pp_lds_bytes(cc, mt, ks, stride, nch, 1) <= DY_WLDS_BUDGET ? 1 : 0;
-}
-// ---- the streaming 1x1 kernel (conv1x1_stream.hip) or the ping-pong kernel's 1x1 branch?
-// DY_CONV1X1_STREAM: 0 = never, force = every launch the kernel supports whatever its size (the tests reach it on small shapes that
-// way), unset = the rule below.
+// ---- the plan of one launch
+static bool g_no_dg2 = getenv("DY_CONV_NO_DG2") != nullptr;
+// DY_CONV1X1_STREAM: 0 = never, force = every launch the stream kernel supports whatever its size (the tests reach it on small shapes
+// that way), unset = from DY_STREAM_MIN_PIX pixels on
 #define DY_STREAM_MIN_PIX 8192  // smallest launch the unset rule gives the stream kernel (between the measured tie at 6400 and win at 25600)
-static int conv1x1_stream_mode() {
-  static const int mode = [] {
-    const char* e = getenv("DY_CONV1X1_STREAM");
-    if (!e) return 1;
-    if (!strcmp(e, "0")) return 0;
-    return !strcmp(e, "force") ? 2 : 1;
-  }();
-  return mode;
+static const int g_stream_mode = [] {
+  const char* e = getenv("DY_CONV1X1_STREAM");
+  return !e ? 1 : (!strcmp(e, "0") ? 0 : (!strcmp(e, "force") ? 2 : 1));
+}();
+static size_t dg2_lds_bytes(int cc, int mt, int nch) {
+  return (size_t)nch * 9 * (cc / 32) * 16 * mt * 64 + 2 * (size_t)(5 * 17 * ps_bytes(cc, 1)) + 8 * 16 * (size_t)(32 * mt + 16);
 }
-// k-steps of 32 and the cout-group width the stream kernel would run this layer with (the geometry the weights are packed for); false:
-// the weights do not fit its register plan (more than DY_STREAM_MAX_KSTEPS k-steps, or 8-channel chunks)
-static bool conv1x1_stream_shape(int cin, int cout, int* nks, int* mt, int* ngroups, int* cpk) {
-  int cp, op, cc, nch, m, ng, kst, pe;
-  if (dy_conv_geometry(cin, cout, 1, 1, &cp, &op, &cc, &nch, &m, &ng, &kst, &pe) != DY_OK || cin != cp || cc < 16) return false;
-  *nks = nch * kst;
-  *mt = m;
-  *ngroups = ng;
-  *cpk = cc < 32 ? cc : 32;
-  return conv1x1_stream_has(*nks, m) != 0;
-}
-static bool segs_valid(const DySegs* s, int total);
-static int segs_chunk(int cin, int cout, const DySegs* s);
-// the Cin chunk the ping-pong kernel would stage this launch with (0: none)
-static int conv1x1_pp_chunk(int cin, int cout, const DySegs* xs) {
-  if (xs) return segs_chunk(cin, cout, xs);
-  int cp, op, cc, nch, m, ng, kst, pe;
-  return dy_conv_geometry(cin, cout, 1, 1, &cp, &op, &cc, &nch, &m, &ng, &kst, &pe) == DY_OK ? cc : 0;
-}
-// Does this 1x1 launch take the stream kernel?  Supported: fp16 store, DY_EPI_ACCUM, DY_EPI_STATS | DY_EPI_STATS_ACC; plain or segmented
-// input (whatever dy_conv1x1_segs_supported accepts, up-sampled members below 2^24 pixels); plain or segmented output.  Everything else
-// -- partial-row statistics, fp32 output, bias / SiLU / residual epilogues -- stays with the ping-pong kernel.
-static bool conv1x1_stream_wanted(int cin, int cout, int npix, int epi, const DySegs* xs, const DySegs* ys) {
-  const int mode = conv1x1_stream_mode();
-  if (!mode || npix <= 0) return false;
-  int nks, mt, ng, cpk;
-  if (!conv1x1_stream_shape(cin, cout, &nks, &mt, &ng, &cpk) || cout % 8) return false;
-  if (!(epi == 0 || epi == DY_EPI_ACCUM || epi == (DY_EPI_STATS | DY_EPI_STATS_ACC))) return false;
-  if (xs) {
-    if (!segs_valid(xs, cin) || !segs_chunk(cin, cout, xs)) return false;
-    for (int k = 0; k < xs->nseg; ++k)
-      if ((xs->acc[k] & 2) && npix >= (1 << 24)) return false;
-  }
-  if (ys && (epi || !segs_valid(ys, cout))) return false;
-  if (epi & DY_EPI_STATS) {  // the sums are taken on the ping-pong kernel's 256-pixel tiles (conv1x1_stream_kernel, PP): it must be the
-    const int c = conv1x1_pp_chunk(cin, cout, xs);  // kernel this launch would otherwise run, with 64 pixels per wave
-    if (!c || cin % c || pp_trows(c, mt, 1, 1, cin / c) != 2) return false;
-  }
-  if (mode == 2) return true;
-  // The rule (per-shape table of profiles/r05_conv1x1_stream.md): at batch 64 the stream kernel wins on every map (160x160
-  // -9 %, 80x80 -22...-43 %, 40x40 -10...-26 %, 20x20 = 25600 pixels -14 %).  From 400 to 6400 pixels both kernels sit on the ~8 us launch
-  // floor: the 32- and 64-channel shapes tie within the +-0.3 us repeat noise (the 128-channel ones gain 1.5-2 us), nothing a step could
-  // show.  Launches that small keep the ping-pong kernel.
-  return npix >= DY_STREAM_MIN_PIX;
-}
-
 // workgroups of a ping-pong launch: every workgroup resident at once (one per CU, two when two fit in LDS), each owning
 // two tiles per period; this is also the number of BN partial rows the launch writes
 static int pp_grid(int cc, int mt, int ks, int stride, int nch, int trows, int ntiles, int fw = 0) {
@@ -1915,174 +1812,17 @@ static int pp_grid(int cc, int mt, int ks, int stride, int nch, int trows, int n
   if (want >= 8) want = (want + 7) & ~7;  // a multiple of the XCD count, so that the XCD-aware tile map applies
   return want < cap ? want : cap;
 }
-
-// full-width tiles (conv_mfma_pp_kernel, FW): maps exactly 40 / 80 pixels wide, 3x3 stride-1 with 32-channel chunks.  DY_CONV_FW=0: off
-template <int MT, int FW>
-static int launch_pp_fw(const ConvArgs& a, int grid_y, hipStream_t s) {
-  constexpr int TR = 80 / FW;
-  static bool attr_set = false;
-  auto kern = conv_mfma_pp_kernel<32, MT, 3, 1, TR, false, FW>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, DY_WLDS_BUDGET) != hipSuccess)
-      return DY_ERR_LAUNCH;
-    attr_set = true;
-  }
-  ConvArgs b = a;
-  b.tiles_x = 1;
-  b.tiles_y = cdiv(a.Ho, 4 * TR);
-  const int ntiles = b.tiles_y * a.N;
-  const int gx = pp_grid(32, MT, 3, 1, a.nch, TR, ntiles, FW);
-  hipLaunchKernelGGL(kern, dim3(gx, grid_y), dim3(512), pp_lds_bytes(32, MT, 3, 1, a.nch, TR, FW), s, b, ntiles);
-  DY_CHECK_LAUNCH();
-  return DY_OK;
-}
+// full-width tiles (conv_mfma_pp_kernel, FW): maps exactly 40 / 80 pixels wide, 3x3 stride-1 with 32-channel chunks.
 // DY_CONV_FW: 0 = off, 40 (default) = 40-wide maps, 80 = 40- and 80-wide maps (measured on the step: 80-wide tiles gain nothing --
 // 32->32 @80x80 19.3 -> 18.3 us stand-alone, 11.43 vs 11.44 ms per step -- so they stay behind the switch)
 static int pp_fw_for(int cc, int mt, int ks, int stride, int nch, int wo, int dil, int epi, bool red) {
   static const int on = getenv("DY_CONV_FW") ? atoi(getenv("DY_CONV_FW")) : 40;
   if (!on || ks != 3 || stride != 1 || cc != 32 || dil == 2 || red) return 0;
-  if ((epi & DY_EPI_STATS) && !(epi & DY_EPI_STATS_ACC)) return 0;  // partial-row statistics: dy_conv_num_partials sizes the rows for the 32-wide tiles
+  if ((epi & DY_EPI_STATS) && !(epi & DY_EPI_STATS_ACC)) return 0;  // partial-row statistics: ConvPlan::partials counts 32-wide tiles
   const int fw = wo == 40 ? 40 : ((wo == 80 && on >= 80) ? 80 : 0);
   if (!fw || pp_lds_bytes(cc, mt, ks, stride, nch, 80 / fw, fw) > DY_WLDS_BUDGET) return 0;
   return fw;
 }
-static int pp_fw_width(const ConvArgs& a, int cc, int mt, int ks, int stride) {
-  if (a.Wo != a.Wr || a.Ho != a.Hr) return 0;
-  return pp_fw_for(cc, mt, ks, stride, a.nch, a.Wo, a.dil, a.epi, a.racc != nullptr);
-}
-
-template <int CC, int MT, int KS, int STRIDE, int TR, bool REDK = false>
-static int launch_pp(const ConvArgs& a, int grid_y, hipStream_t s) {
-  if constexpr (CC == 32 && KS == 3 && STRIDE == 1 && !REDK) {
-    const int fw = pp_fw_width(a, CC, MT, KS, STRIDE);
-    if (fw == 40) return launch_pp_fw<MT, 40>(a, grid_y, s);
-    if (fw == 80) return launch_pp_fw<MT, 80>(a, grid_y, s);
-  }
-  if (!REDK && a.racc) {  // the epilogue that also runs a BatchNorm backward reduce: its own instantiation (stride-1 dgrads only), so
-    if constexpr (STRIDE == 1) return launch_pp<CC, MT, KS, 1, TR, true>(a, grid_y, s);  // that its registers are not every launch's problem
-    return DY_ERR_ARG;
-  }
-  static bool attr_set = false;
-  auto kern = conv_mfma_pp_kernel<CC, MT, KS, STRIDE, TR, REDK>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, DY_WLDS_BUDGET) != hipSuccess)
-      return DY_ERR_LAUNCH;
-    attr_set = true;
-  }
-  ConvArgs b = a;
-  int ntiles;
-  if (KS == 1) {
-    ntiles = cdiv(a.npix, 4 * 2 * TR * 16);
-  } else {
-    b.tiles_y = cdiv(a.Ho, 4 * TR);
-    ntiles = b.tiles_x * b.tiles_y * a.N;
-  }
-  const int gx = pp_grid(CC, MT, KS, STRIDE, a.nch, TR, ntiles);
-  hipLaunchKernelGGL(kern, dim3(gx, grid_y), dim3(512), pp_lds_bytes(CC, MT, KS, STRIDE, a.nch, TR), s, b, ntiles);
-  DY_CHECK_LAUNCH();
-  return DY_OK;
-}
-
-template <int CC, int MT, int KS, int STRIDE, int TROWS>
-static int launch_conv(const ConvArgs& a, int grid_x, int grid_y, hipStream_t s) {
-  const int pp = pp_trows(CC, MT, KS, STRIDE, a.nch);
-  if (pp == 2 && !(KS == 3 && STRIDE == 2)) return launch_pp<CC, MT, KS, STRIDE, (KS == 3 && STRIDE == 2) ? 1 : 2>(a, grid_y, s);
-  if (pp == 1) return launch_pp<CC, MT, KS, STRIDE, 1>(a, grid_y, s);
-  const int cfg = (g_force_v1 || (CC == 64 && STRIDE == 2)) ? 0 : v3_trows(CC, MT, KS, STRIDE, a.nch);
-  if (cfg == 2 && !(KS == 3 && STRIDE == 2)) return launch_v3<CC, MT, KS, STRIDE, (KS == 3 && STRIDE == 2) ? 1 : 2, 8>(a, grid_y, s);
-  if (cfg == 4 && KS == 3 && STRIDE == 1) return launch_v3<CC, MT, KS, STRIDE, (KS == 3 && STRIDE == 1) ? 2 : 1, (KS == 3 && STRIDE == 1) ? 4 : 8>(a, grid_y, s);
-  if (cfg == 1) return launch_v3<CC, MT, KS, STRIDE, 1, 8>(a, grid_y, s);
-  hipLaunchKernelGGL((conv_mfma_kernel<CC, MT, KS, STRIDE, TROWS>), dim3(grid_x, grid_y), dim3(256), 0, s, a);
-  DY_CHECK_LAUNCH();
-  return DY_OK;
-}
-
-template <int KS, int STRIDE, int TROWS>
-static int dispatch_cc_mt(int cc, int mt, const ConvArgs& a, int gx, int gy, hipStream_t s) {
-#define DY_CASE(C, M) \
-  if (cc == C && mt == M) return launch_conv<C, M, KS, STRIDE, TROWS>(a, gx, gy, s);
-  DY_CASE(8, 1) DY_CASE(8, 2) DY_CASE(8, 4)
-  DY_CASE(16, 1) DY_CASE(16, 2) DY_CASE(16, 4)
-  DY_CASE(32, 1) DY_CASE(32, 2) DY_CASE(32, 4)
-  if (STRIDE == 1) { DY_CASE(64, 1) DY_CASE(64, 2) DY_CASE(64, 4) }
-#undef DY_CASE
-  return DY_ERR_ARG;
-}
-
-extern "C" int dy_conv_num_partials(int n, int h, int w, int cin, int cout, int ks, int stride, int dil);
-
-static bool g_no_dg2 = getenv("DY_CONV_NO_DG2") != nullptr;
-static size_t dg2_lds_bytes(int cc, int mt, int nch) {
-  return (size_t)nch * 9 * (cc / 32) * 16 * mt * 64 + 2 * (size_t)(5 * 17 * ps_bytes(cc, 1)) + 8 * 16 * (size_t)(32 * mt + 16);
-}
-template <int CC, int MT>
-static int launch_dg2(const ConvArgs& a, int grid_y, hipStream_t s) {
-  static bool attr_set = false;
-  auto kern = conv_mfma_dg2_kernel<CC, MT>;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, DY_WLDS_BUDGET) != hipSuccess)
-      return DY_ERR_LAUNCH;
-    attr_set = true;
-  }
-  ConvArgs b = a;
-  b.tiles_x = cdiv(a.Wo, 32);
-  b.tiles_y = cdiv(a.Ho, 8);
-  const int ntiles = b.tiles_x * b.tiles_y * a.N;
-  const size_t lds = dg2_lds_bytes(CC, MT, a.nch);
-  const int per_cu = 2 * lds <= 160 * 1024 ? 2 : 1;
-  int gx = cdiv(ntiles, 2);
-  if (gx > DY_NUM_CUS * per_cu) gx = DY_NUM_CUS * per_cu;
-  hipLaunchKernelGGL(kern, dim3(gx, grid_y), dim3(512), lds, s, b, ntiles);
-  DY_CHECK_LAUNCH();
-  return DY_OK;
-}
-
-struct RedHost { const void* raw; int ldraw; const float* coef; double* acc; int C; const void* res; int ldres;
-                 const DySegs* xs; const DySegs* ys; int cc_override; };
-static int conv_forward_impl(const void* x, int ldx, const void* w_packed, const float* bias, void* y, int ldy,
-                             float* partials, int n, int h, int w, int cin, int cout, int ks, int stride, int dil,
-                             int out_h, int out_w, int epi, int* num_partials, hipStream_t stream, const RedHost* red);
-extern "C" int dy_conv_forward(const void* x, int ldx, const void* w_packed, const float* bias, void* y, int ldy,
-                               float* partials, int n, int h, int w, int cin, int cout, int ks, int stride, int dil,
-                               int out_h, int out_w, int epi, int* num_partials, hipStream_t stream) {
-  return conv_forward_impl(x, ldx, w_packed, bias, y, ldy, partials, n, h, w, cin, cout, ks, stride, dil, out_h, out_w, epi, num_partials,
-                           stream, nullptr);
-}
-// 1 when dy_conv_input_grad_red can take this (stride-1) input-gradient geometry: the ping-pong kernel with its transposing epilogue
-extern "C" int dy_conv_red_supported(int cin, int cout, int ks) {
-  int cp, op, cc, nch, mt, ng, kst, pe;
-  if (dy_conv_geometry(cin, cout, ks, 1, &cp, &op, &cc, &nch, &mt, &ng, &kst, &pe) != DY_OK) return 0;
-  return (cin == cp && cout % 8 == 0 && pp_trows(cc, mt, ks, 1, nch) != 0) ? 1 : 0;
-}
-// The input gradient of a stride-1 convolution (dy_conv_forward over the transposed pack, no epilogue flags) that is the ONLY writer of
-// the gradient it produces -- the gradient w.r.t. the activated output of a Conv (conv + BatchNorm + SiLU) -- and therefore also runs
-// the first pass of that Conv's BatchNorm backward on the values it stores: sums of g = dy * silu'(raw * scale + shift) and g * xhat,
-// added into acc [DY_BN_COPIES][2][C] (what dy_bn_act_bwd_reduce_acc would compute from the stored tensor in a pass of its own).
-extern "C" int dy_conv_input_grad_red(const void* dy, int lddy, const void* w_packed_t, void* dx, int lddx, int n, int h, int w, int cin,
-                                      int cout, int ks, const void* raw, int ldraw, const float* coef, double* acc, int C,
-                                      hipStream_t stream) {
-  if (!raw || !coef || !acc || C != cout || (ldraw & 7) || ((uintptr_t)raw & 15) || !dy_conv_red_supported(cin, cout, ks) || (lddx & 7))
-    return DY_ERR_ARG;
-  const RedHost red{raw, ldraw, coef, acc, C, nullptr, 0, nullptr, nullptr, 0};
-  return conv_forward_impl(dy, lddy, w_packed_t, nullptr, dx, lddx, nullptr, n, h, w, cin, cout, ks, 1, 1, 0, 0, 0, nullptr, stream, &red);
-}
-// 1 when dy_conv_forward_res can take this geometry: the ping-pong kernel's transposing epilogue (whole 8-channel pieces)
-extern "C" int dy_conv_res_supported(int cin, int cout, int ks, int stride) {
-  int cp, op, cc, nch, mt, ng, kst, pe;
-  if (dy_conv_geometry(cin, cout, ks, stride, &cp, &op, &cc, &nch, &mt, &ng, &kst, &pe) != DY_OK) return 0;
-  return (ks == 3 && stride == 1 && cin == cp && cout % 8 == 0 && pp_trows(cc, mt, ks, stride, nch) != 0) ? 1 : 0;
-}
-// Conv.forward_fuse followed by Bottleneck's shortcut add (reference nn/modules/conv.py:57-59, nn/modules/block.py:333-335) in one
-// launch: y = fp16(fp16(SiLU(conv(x) + bias)) + res) -- the bits of dy_conv_forward(BIAS | SILU) followed by dy_add.
-extern "C" int dy_conv_forward_res(const void* x, int ldx, const void* w_packed, const float* bias, const void* res, int ldres, void* y,
-                                   int ldy, int n, int h, int w, int cin, int cout, int ks, int stride, hipStream_t stream) {
-  if (!res || !bias || (ldres & 7) || ((uintptr_t)res & 15) || (ldy & 7) || !dy_conv_res_supported(cin, cout, ks, stride)) return DY_ERR_ARG;
-  const RedHost red{nullptr, 0, nullptr, nullptr, 0, res, ldres, nullptr, nullptr, 0};
-  return conv_forward_impl(x, ldx, w_packed, bias, y, ldy, nullptr, n, h, w, cin, cout, ks, stride, 1, 0, 0,
-                           DY_EPI_BIAS | DY_EPI_SILU | DY_EPI_RES, nullptr, stream, &red);
-}
-// ---- 1x1 convolutions over a never-materialised concatenation (DySegs)
-extern "C" int dy_segs_bytes(void) { return (int)sizeof(DySegs); }
 static bool segs_valid(const DySegs* s, int total) {
   if (!s || s->nseg < 1 || s->nseg > DY_MAX_SEGS || s->c_end[s->nseg - 1] != total) return false;
   for (int k = 0; k < s->nseg; ++k) {
@@ -2091,205 +1831,392 @@ static bool segs_valid(const DySegs* s, int total) {
   }
   return true;
 }
-// the Cin chunk a forward launch over these segments stages per step: dy_conv_geometry's own, or 32 where that one (64) would straddle
+// the Cin chunk a 1x1 launch over these input segments stages per step: the geometry's own, or 32 where that one (64) would straddle
 // a boundary -- the packed weights are the same for both; 0: no such chunk (16-channel chunks of 48- / 80-channel inputs only work
-// when they are the geometry's own)
-static int segs_chunk(int cin, int cout, const DySegs* s) {
-  int cp, op, cc, nch, mt, ng, kst, pe;
-  if (dy_conv_geometry(cin, cout, 1, 1, &cp, &op, &cc, &nch, &mt, &ng, &kst, &pe) != DY_OK || cin != cp) return 0;
-  for (int c = cc; c >= 32 || c == cc; c >>= 1) {
-    bool ok = cin % c == 0 && cin / c <= 16 && pp_trows(c, mt, 1, 1, cin / c) != 0;
+// when they are the geometry's own).  At most 16 chunks: the kernel's per-chunk table.
+static int segs_chunk(const ConvGeom& g, int cin, const DySegs* s) {
+  if (cin != g.cin_p) return 0;
+  for (int c = g.cc; c >= 32 || c == g.cc; c >>= 1) {
+    bool ok = cin % c == 0 && cin / c <= 16 && pp_trows(c, g.mt, 1, 1, cin / c) != 0;
     for (int k = 0; ok && k < s->nseg; ++k) ok = s->c_end[k] % c == 0;
     if (ok) return c;
     if (c <= 32) break;
   }
   return 0;
 }
-extern "C" int dy_conv1x1_segs_supported(int cin, int cout, const DySegs* xs) {
-  return (segs_valid(xs, cin) && segs_chunk(cin, cout, xs) != 0) ? 1 : 0;
+
+enum ConvFamily { CONV_PP, CONV_PP_FW, CONV_V3, CONV_V1, CONV_DG2, CONV_STREAM };
+// What a question admits besides the base family (ping-pong, v3 or v1 by LDS fit).  The launcher asks for everything; the planning
+// helpers see no tensors and each asks for what its contract names.
+enum { ASK_FW = 1, ASK_DG2 = 2, ASK_STREAM = 4, ASK_TENSORS = 8, ASK_LAUNCH = 15 };
+struct ConvQuery {
+  int cin, cout, ks, stride, dil;
+  int n, h, w, out_h, out_w;  // the input map; out_h, out_w > 0: the output extent of a stride-2 dgrad, which h cannot tell
+  int epi;
+  bool red, res;              // the epilogue also runs a BatchNorm backward reduce / adds a residual
+  const DySegs *xs, *ys;      // 1x1: segmented input / output
+  int ask;
+  // ASK_TENSORS only: the input pitch, the alignment dy_conv_forward documents, whether y and ldy allow the transposing epilogue's
+  // 16-byte stores, whether a partials buffer was passed
+  int ldx;
+  bool io_aligned, y_vec8, has_partials;
+};
+static ConvQuery conv_query(int cin, int cout, int ks, int stride, int ask) {
+  ConvQuery q{};
+  q.cin = cin; q.cout = cout; q.ks = ks; q.stride = stride; q.dil = 1; q.ask = ask;
+  return q;
 }
-// the instantiation dy_conv1x1_forward_segs launches for these segments, spelled as rocprofv3 prints it (see dy_conv_kernel_name)
-extern "C" int dy_conv1x1_segs_kernel_name(int cin, int cout, const DySegs* xs, char* out, int cap) {
-  if (!out || cap < 8 || !segs_valid(xs, cin)) return DY_ERR_ARG;
-  const int c = segs_chunk(cin, cout, xs);
-  int cp, op, cc, nch, mt, ng, kst, pe;
-  if (!c || dy_conv_geometry(cin, cout, 1, 1, &cp, &op, &cc, &nch, &mt, &ng, &kst, &pe) != DY_OK) return DY_ERR_ARG;
-  const int pp = pp_trows(c, mt, 1, 1, cin / c);
-  if (!pp) return DY_ERR_ARG;
-  snprintf(out, cap, "conv_mfma_pp_kernel<%d, %d, 1, 1, %d, false, 0>", c, mt, pp);
+struct ConvPlan {
+  int err;                // DY_OK, or what the launcher returns
+  ConvFamily fam;
+  ConvGeom g;             // how the weights are packed
+  int cc, nch;            // the Cin chunks staged (a segmented input may halve the geometry's 64)
+  int tr, fw;             // template arguments: rows per wave (v1: TROWS); full tile width
+  bool redk;
+  int nks, cpk;           // stream kernel: 32-channel k-steps, real channels per k-step
+  int Ho, Wo, npix;       // output map; 1x1: pixels of the launch
+  int tiles_x, tiles_y, ntiles;
+  int gx, gy, block;      // (stream kernel without statistics: conv1x1_stream_launch sizes gx itself)
+  size_t lds;
+  int partials;           // partial rows of a DY_EPI_STATS launch: the base family's grid x (v1: tiles) on 32-wide tiles
+};
+static ConvPlan conv_plan(const ConvQuery& q) {
+  ConvPlan p{};
+  const bool tensors = q.ask & ASK_TENSORS;
+  const int pad = q.ks / 2, st = q.stride ? q.stride : 1;  // (a stride of 0 is refused below)
+  p.Ho = ((q.dil == 2 ? 2 * q.h : q.h) + 2 * pad - q.ks) / st + 1;
+  p.Wo = ((q.dil == 2 ? 2 * q.w : q.w) + 2 * pad - q.ks) / st + 1;
+  // tiles and grid of the base families over p.Ho x p.Wo; every tile is 32 pixels wide (1x1: 32 * rows pixels)
+  auto tile = [&] {
+    const int rows = p.fam == CONV_PP ? 4 * p.tr : (p.fam == CONV_V3 ? 8 * p.tr : (q.stride == 1 ? 8 : 4));
+    if (q.ks == 1) {
+      p.npix = (double)q.n * p.Ho * p.Wo < 2147483648.0 ? q.n * p.Ho * p.Wo : 0;
+      p.ntiles = cdiv(p.npix, 32 * rows);
+    } else {
+      p.tiles_x = cdiv(p.Wo, 32);
+      p.tiles_y = cdiv(p.Ho, rows);
+      p.ntiles = p.tiles_x * p.tiles_y * q.n;
+    }
+    p.gx = p.fam == CONV_PP ? pp_grid(p.cc, p.g.mt, q.ks, q.stride, p.nch, p.tr, p.ntiles)
+                            : (p.fam == CONV_V3 && p.ntiles > DY_WLDS_MAX_WGS ? DY_WLDS_MAX_WGS : p.ntiles);
+  };
+  auto fail = [&](int err) { p.err = err; return p; };
+  p.fam = CONV_V1;  // (an unsupported geometry still counts its partial rows, as v1 tiles)
+  tile();
+  p.partials = p.gx;
+  p.g = conv_geom(q.cin, q.cout, q.ks, q.stride);
+  if (p.g.rc != DY_OK) return fail(DY_ERR_ARG);
+  const ConvGeom& g = p.g;
+  p.cc = g.cc;
+  p.nch = g.nch;
+  if (q.xs) {  // the chunk is chosen so that none straddles two segments; same packed layout
+    if (q.ks != 1 || !segs_valid(q.xs, q.cin) || !(p.cc = segs_chunk(g, q.cin, q.xs))) return fail(DY_ERR_ARG);
+    p.nch = q.cin / p.cc;
+    for (int k = 0; tensors && k < q.xs->nseg; ++k)  // an up-sampled member (acc bit 1) halves both map sides; 32-bit buffer offsets
+      if (((q.xs->acc[k] & 2) && ((q.h | q.w) & 1)) || (double)q.n * q.h * q.w * q.xs->ld[k] * 2.0 >= 2147483648.0) return fail(DY_ERR_ARG);
+  }
+  if (q.ys && (q.ks != 1 || q.epi || !segs_valid(q.ys, q.cout))) return fail(DY_ERR_ARG);
+
+  // base family: the ping-pong kernel where the weights and two tiles fit in LDS, else v3, else v1
+  const int pp = pp_trows(p.cc, g.mt, q.ks, q.stride, p.nch), v3 = pp ? 0 : v3_trows(p.cc, g.mt, q.ks, q.stride, p.nch);
+  p.fam = pp ? CONV_PP : (v3 ? CONV_V3 : CONV_V1);
+  p.tr = pp ? pp : (v3 ? v3 : ((q.ks == 3 && q.stride == 2) ? 1 : 2));
+  p.redk = q.red;
+  // a reduce, a residual or segments ride the ping-pong kernel's transposing epilogue (whole 8-channel pieces) only
+  if ((q.red || q.res) && (p.fam != CONV_PP || q.cin != g.cin_p || q.cout % 8 || q.stride != 1 || (q.res && q.ks != 3))) return fail(DY_ERR_ARG);
+  if (q.ys && tensors && p.fam != CONV_PP) return fail(DY_ERR_ARG);
+  if (tensors) {
+    if (q.cin != g.cin_p || !q.io_aligned) return fail(DY_ERR_ALIGN);
+    if (q.dil != 1 && !(q.dil == 2 && q.ks == 3 && q.stride == 1)) return fail(DY_ERR_ARG);
+    // the staging loads address the input through 32-bit buffer offsets: the whole tensor (1x1) or one image (3x3) must stay
+    // below 2 GiB -- fail loudly rather than wrap
+    if ((q.ks == 1 ? (double)q.n : 1.0) * q.h * q.w * q.ldx * 2.0 >= 2147483648.0) return fail(DY_ERR_ARG);
+    if ((q.epi & DY_EPI_STATS) && !q.has_partials) return fail(DY_ERR_ARG);
+  }
+  tile();
+  p.partials = p.gx;
+  if (tensors && q.out_h > 0 && q.out_w > 0) {
+    if (q.out_h > p.Ho || q.out_w > p.Wo) return fail(DY_ERR_ARG);
+    p.Ho = q.out_h;
+    p.Wo = q.out_w;
+    tile();
+  }
+  if (tensors && p.ntiles <= 0) return fail(DY_ERR_ARG);
+  p.gy = g.ngroups;
+  p.block = p.fam == CONV_V1 ? 256 : 512;
+  p.lds = p.fam == CONV_PP ? pp_lds_bytes(p.cc, g.mt, q.ks, q.stride, p.nch, p.tr)
+                           : (p.fam == CONV_V3 ? wlds_bytes_t(p.cc, g.mt, q.ks, q.stride, p.nch, p.tr) : 0);
+
+  // ---- the alternatives, in the launcher's order of preference
+  // dg2: the input gradient of a stride-2 3x3 (dil == 2) by parity classes; store or accumulate, 8-channel pieces
+  if ((q.ask & ASK_DG2) && q.dil == 2 && !g_no_dg2 && !g_force_v1 && (p.cc == 32 || p.cc == 64) && !(q.epi & ~DY_EPI_ACCUM) && q.y_vec8 &&
+      q.cout % 8 == 0 && dg2_lds_bytes(p.cc, g.mt, p.nch) <= DY_WLDS_BUDGET && (double)q.h * q.w * q.ldx * 2.0 < 2147483648.0) {
+    p.fam = CONV_DG2;
+    p.block = 512;
+    p.lds = dg2_lds_bytes(p.cc, g.mt, p.nch);
+    p.tiles_x = cdiv(p.Wo, 32);
+    p.tiles_y = cdiv(p.Ho, 8);
+    p.ntiles = p.tiles_x * p.tiles_y * q.n;
+    const int cap = DY_NUM_CUS * (2 * p.lds <= 160 * 1024 ? 2 : 1);
+    p.gx = cdiv(p.ntiles, 2) < cap ? cdiv(p.ntiles, 2) : cap;
+    return p;
+  }
+  // The streaming 1x1 kernel (conv1x1_stream.hip, DESIGN 4.9 for the measurements behind the size rule): weights that fit its register
+  // plan (at most DY_STREAM_MAX_KSTEPS k-steps, no 8-channel chunks); fp16 store, DY_EPI_ACCUM or DY_EPI_STATS | DY_EPI_STATS_ACC; plain or
+  // segmented input (up-sampled members below 2^24 pixels) and output.  Its statistics are summed on the ping-pong kernel's 256-pixel
+  // tiles and grid, so that must be the kernel the launch would otherwise run, with 64 pixels per wave.  Everything else -- partial-row
+  // statistics, fp32 output, bias / SiLU / residual / reduce epilogues, launches below DY_STREAM_MIN_PIX -- stays with the base family.
+  const int mode = g_stream_mode;
+  bool stream = (q.ask & ASK_STREAM) && q.ks == 1 && mode && p.npix > 0 && !q.red && !q.res && q.y_vec8 && q.cin == g.cin_p && g.cc >= 16 &&
+                conv1x1_stream_has(g.nch * g.ksteps, g.mt) && q.cout % 8 == 0 &&
+                (q.epi == 0 || q.epi == DY_EPI_ACCUM || q.epi == (DY_EPI_STATS | DY_EPI_STATS_ACC)) &&
+                (!(q.epi & DY_EPI_STATS) || (p.fam == CONV_PP && p.tr == 2)) && (mode == 2 || p.npix >= DY_STREAM_MIN_PIX);
+  for (int k = 0; stream && q.xs && k < q.xs->nseg; ++k) stream = !((q.xs->acc[k] & 2) && p.npix >= (1 << 24));
+  if (stream) {
+    p.fam = CONV_STREAM;
+    p.nks = g.nch * g.ksteps;
+    p.cpk = g.cc < 32 ? g.cc : 32;
+    p.lds = 0;
+    p.block = (q.epi & DY_EPI_STATS) ? 512 : 256;
+    if (!(q.epi & DY_EPI_STATS)) p.gx = 0;  // (with statistics: the ping-pong grid computed above)
+    return p;
+  }
+  if ((q.ask & ASK_FW) && p.fam == CONV_PP && p.Wo == q.w && p.Ho == q.h)
+    p.fw = pp_fw_for(p.cc, g.mt, q.ks, q.stride, p.nch, p.Wo, q.dil, q.epi, q.red);
+  if (p.fw) {
+    p.fam = CONV_PP_FW;
+    p.tr = 80 / p.fw;
+    p.tiles_x = 1;
+    p.tiles_y = cdiv(p.Ho, 4 * p.tr);
+    p.ntiles = p.tiles_y * q.n;
+    p.gx = pp_grid(p.cc, g.mt, q.ks, q.stride, p.nch, p.tr, p.ntiles, p.fw);
+    p.lds = pp_lds_bytes(p.cc, g.mt, q.ks, q.stride, p.nch, p.tr, p.fw);
+  }
+  return p;
+}
+// the instantiation a plan runs, spelled as rocprofv3 prints it
+static int plan_name(const ConvPlan& p, const ConvQuery& q, char* out, int cap) {
+  if (!out || cap < 8 || p.err != DY_OK) return DY_ERR_ARG;
+  switch (p.fam) {
+    case CONV_PP:
+    case CONV_PP_FW:
+      snprintf(out, cap, "conv_mfma_pp_kernel<%d, %d, %d, %d, %d, %s, %d>", p.cc, p.g.mt, q.ks, q.stride, p.tr, p.redk ? "true" : "false", p.fw);
+      break;
+    case CONV_V3: snprintf(out, cap, "conv_mfma_wlds_kernel<%d, %d, %d, %d, %d, 8>", p.cc, p.g.mt, q.ks, q.stride, p.tr); break;
+    case CONV_V1: snprintf(out, cap, "conv_mfma_kernel<%d, %d, %d, %d, %d>", p.cc, p.g.mt, q.ks, q.stride, p.tr); break;
+    case CONV_DG2: snprintf(out, cap, "conv_mfma_dg2_kernel<%d, %d>", p.cc, p.g.mt); break;
+    case CONV_STREAM: snprintf(out, cap, "conv1x1_stream_kernel<%d, %d, %s>", p.nks, p.g.mt, (q.epi & DY_EPI_STATS) ? "true" : "false"); break;
+  }
   return DY_OK;
 }
-// dy_conv_forward for a 1x1 convolution whose INPUT is the concatenation xs (n, h, w, cin = xs->c_end[last]): Conv.forward over
-// torch.cat(...) (reference nn/modules/block.py:222-226 C2f, :166-171 SPPF, nn/modules/conv.py:338-348 Concat) without the cat.
-extern "C" int dy_conv1x1_forward_segs(const DySegs* xs, const void* w_packed, const float* bias, void* y, int ldy, float* partials, int n,
-                                       int h, int w, int cin, int cout, int epi, hipStream_t stream) {
-  if (!segs_valid(xs, cin)) return DY_ERR_ARG;
-  const int c = segs_chunk(cin, cout, xs);
-  if (!c) return DY_ERR_ARG;
-  for (int k = 0; k < xs->nseg; ++k)  // an up-sampled member (acc bit 1) halves both map sides
-    if ((xs->acc[k] & 2) && ((h | w) & 1)) return DY_ERR_ARG;
-  const RedHost red{nullptr, 0, nullptr, nullptr, 0, nullptr, 0, xs, nullptr, c};
-  return conv_forward_impl(nullptr, 0, w_packed, bias, y, ldy, partials, n, h, w, cin, cout, 1, 1, 1, 0, 0, epi, nullptr, stream, &red);
+
+// ---- launching what the plan says
+template <auto KERN>  // a kernel with dynamic LDS and (ConvArgs, ntiles) parameters: ping-pong, v3, dg2
+static int launch_planned(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  static bool attr_set = false;
+  if (!attr_set) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, DY_WLDS_BUDGET) != hipSuccess)
+      return DY_ERR_LAUNCH;
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(KERN, dim3(p.gx, p.gy), dim3(p.block), p.lds, s, a, p.ntiles);
+  DY_CHECK_LAUNCH();
+  return DY_OK;
 }
-// ... and its input gradient: dx_s (+)= (W^T dy)[channels of segment s] for every segment of dxs (total channels = cout here),
-// stored or added per segment (dxs->acc): the dgrad of the same layer writing straight into the concat members' gradient tensors.
-extern "C" int dy_conv1x1_input_grad_segs(const void* dy, int lddy, const void* w_packed_t, const DySegs* dxs, int n, int h, int w, int cin,
-                                          int cout, hipStream_t stream) {
-  if (!segs_valid(dxs, cout)) return DY_ERR_ARG;
-  const RedHost red{nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, dxs, 0};
-  return conv_forward_impl(dy, lddy, w_packed_t, nullptr, nullptr, 0, nullptr, n, h, w, cin, cout, 1, 1, 1, 0, 0, 0, nullptr, stream, &red);
+// The instantiations of one (CC, MT, KS, STRIDE): each tiled family with TR rows per wave (2; stride-2 3x3: 1) and with 1.  The epilogue
+// that also runs a BatchNorm backward reduce (REDK) is its own instantiation, stride-1 dgrads only, so that its registers are not every
+// launch's problem; full-width tiles exist for 3x3 stride-1 over 32-channel chunks.
+template <int CC, int MT, int KS, int STRIDE>
+static int launch_conv(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+  constexpr int TR = (KS == 3 && STRIDE == 2) ? 1 : 2;
+  const bool tall = p.tr == TR;
+  if (p.fam == CONV_PP_FW) {
+    if constexpr (CC == 32 && KS == 3 && STRIDE == 1)
+      return p.fw == 40 ? launch_planned<conv_mfma_pp_kernel<32, MT, 3, 1, 2, false, 40>>(a, p, s) : launch_planned<conv_mfma_pp_kernel<32, MT, 3, 1, 1, false, 80>>(a, p, s);
+  } else if (p.fam == CONV_PP && p.redk) {
+    if constexpr (STRIDE == 1)
+      return tall ? launch_planned<conv_mfma_pp_kernel<CC, MT, KS, 1, TR, true>>(a, p, s) : launch_planned<conv_mfma_pp_kernel<CC, MT, KS, 1, 1, true>>(a, p, s);
+  } else if (p.fam == CONV_PP) {
+    return tall ? launch_planned<conv_mfma_pp_kernel<CC, MT, KS, STRIDE, TR>>(a, p, s) : launch_planned<conv_mfma_pp_kernel<CC, MT, KS, STRIDE, 1>>(a, p, s);
+  } else if (p.fam == CONV_V3) {
+    return tall ? launch_planned<conv_mfma_wlds_kernel<CC, MT, KS, STRIDE, TR, 8>>(a, p, s) : launch_planned<conv_mfma_wlds_kernel<CC, MT, KS, STRIDE, 1, 8>>(a, p, s);
+  } else if (p.fam == CONV_V1) {
+    hipLaunchKernelGGL((conv_mfma_kernel<CC, MT, KS, STRIDE, TR>), dim3(p.gx, p.gy), dim3(p.block), 0, s, a);
+    DY_CHECK_LAUNCH();
+    return DY_OK;
+  }
+  return DY_ERR_ARG;
 }
+template <int KS, int STRIDE>
+static int dispatch_cc_mt(const ConvArgs& a, const ConvPlan& p, hipStream_t s) {
+#define DY_CASE(C, M) \
+  if (p.cc == C && p.g.mt == M) return launch_conv<C, M, KS, STRIDE>(a, p, s);
+  DY_CASE(8, 1) DY_CASE(8, 2) DY_CASE(8, 4)
+  DY_CASE(16, 1) DY_CASE(16, 2) DY_CASE(16, 4)
+  DY_CASE(32, 1) DY_CASE(32, 2) DY_CASE(32, 4)
+  if (STRIDE == 1) { DY_CASE(64, 1) DY_CASE(64, 2) DY_CASE(64, 4) }
+#undef DY_CASE
+  return DY_ERR_ARG;
+}
+
+// what rides a launch besides dy_conv_forward's own arguments: a BatchNorm backward reduce, a residual, segmented input / output
+struct RedHost { const void* raw; int ldraw; const float* coef; double* acc; int C; const void* res; int ldres;
+                 const DySegs* xs; const DySegs* ys; };
 static int conv_forward_impl(const void* x, int ldx, const void* w_packed, const float* bias, void* y, int ldy,
                              float* partials, int n, int h, int w, int cin, int cout, int ks, int stride, int dil,
-                             int out_h, int out_w, int epi, int* num_partials, hipStream_t stream, const RedHost* red) {
-  int cp, op, cc, nch, mt, ng, kst, pe;
-  if (dy_conv_geometry(cin, cout, ks, stride, &cp, &op, &cc, &nch, &mt, &ng, &kst, &pe) != DY_OK) return DY_ERR_ARG;
-  const bool segx = red && red->xs, segy = red && red->ys;
-  if (segx) {  // segmented input (1x1): the chunk size the caller chose so that no chunk straddles two segments; same packed layout
-    if (ks != 1 || !red->cc_override || cin % red->cc_override || (red->cc_override != cc && (red->cc_override < 32 || cc < 32))) return DY_ERR_ARG;
-    cc = red->cc_override;
-    nch = cin / cc;
-    if (nch > 16) return DY_ERR_ARG;  // the kernel's per-chunk table
-    x = red->xs->ptr[0];
+                             int out_h, int out_w, int epi, int* num_partials, hipStream_t stream, const RedHost& red) {
+  ConvQuery q = conv_query(cin, cout, ks, stride, ASK_LAUNCH);
+  q.xs = red.xs;
+  q.ys = red.ys;
+  if (q.xs) {  // every segment carries its own pointer and pitch
+    x = q.xs->ptr[0];
     ldx = 8;
-    for (int k = 0; k < red->xs->nseg; ++k)  // every segment is addressed through 32-bit buffer offsets
-      if ((double)n * h * w * red->xs->ld[k] * 2.0 >= 2147483648.0) return DY_ERR_ARG;
   }
-  if (segy) {
-    if (ks != 1 || y || epi) return DY_ERR_ARG;
+  if (q.ys) {
+    if (y) return DY_ERR_ARG;
     ldy = 8;
   }
-  if ((segx || segy) && pp_trows(cc, mt, ks, stride, nch) == 0) return DY_ERR_ARG;
-  if (cin != cp || (ldx & 7) || ((uintptr_t)x & 15) || ((uintptr_t)w_packed & 15)) return DY_ERR_ALIGN;
-  if (!(epi & DY_EPI_F32OUT) && (((uintptr_t)y & 15) || (ldy & 3))) return DY_ERR_ALIGN;
-  if (dil != 1 && !(dil == 2 && ks == 3 && stride == 1)) return DY_ERR_ARG;
-  // the staging loads address the input through 32-bit buffer offsets: the whole tensor (1x1) or one image (3x3) must stay
-  // below 2 GiB -- fail loudly rather than wrap
-  if ((ks == 1 ? (double)n : 1.0) * h * w * ldx * 2.0 >= 2147483648.0) return DY_ERR_ARG;
+  q.dil = dil; q.n = n; q.h = h; q.w = w; q.out_h = out_h; q.out_w = out_w; q.epi = epi;
+  q.red = red.raw != nullptr;
+  q.res = red.res != nullptr;
+  q.ldx = ldx;
+  q.io_aligned = !((ldx & 7) || ((uintptr_t)x & 15) || ((uintptr_t)w_packed & 15)) &&
+                 ((epi & DY_EPI_F32OUT) || !(((uintptr_t)y & 15) || (ldy & 3)));
+  q.y_vec8 = !((uintptr_t)y & 15) && !(ldy & 7);
+  q.has_partials = partials != nullptr;
+  const ConvPlan p = conv_plan(q);
+  if (p.err != DY_OK) return p.err;
+  if (num_partials) *num_partials = p.partials;
+  if (p.fam == CONV_STREAM) {
+    Conv1x1StreamArgs sa{};
+    sa.w = (const f16*)w_packed; sa.y = y; sa.acc = reinterpret_cast<double*>(partials); sa.ldy = ldy; sa.npix = p.npix; sa.cout = cout;
+    sa.epi = epi; sa.cpk = p.cpk; sa.N = n; sa.H = h; sa.W = w;
+    if (q.xs) {
+      sa.xs = *q.xs;
+    } else {  // a plain tensor is one segment
+      sa.xs.nseg = 1; sa.xs.c_end[0] = cin; sa.xs.ld[0] = ldx; sa.xs.acc[0] = 0; sa.xs.ptr[0] = x;
+    }
+    if (q.ys) sa.ys = *q.ys;
+    if (epi & DY_EPI_STATS) sa.pp_grid = p.gx;
+    return conv1x1_stream_launch(sa, p.nks, p.g.mt, p.g.ngroups, stream);
+  }
   ConvArgs a{};
   a.x = (const f16*)x; a.w = (const f16*)w_packed; a.bias = bias; a.y = y; a.partials = partials;
   a.ldx = ldx; a.ldy = ldy; a.N = n; a.Hr = h; a.Wr = w;
   a.H = dil == 2 ? 2 * h : h; a.W = dil == 2 ? 2 * w : w;
-  const int pad = ks / 2;
-  a.Ho = (a.H + 2 * pad - ks) / stride + 1;
-  a.Wo = (a.W + 2 * pad - ks) / stride + 1;
-  if (out_h > 0 && out_w > 0) {  // stride-2 dgrad: the forward input extent (2*h or 2*h-1) cannot be derived from h
-    if (out_h > a.Ho || out_w > a.Wo) return DY_ERR_ARG;
-    a.Ho = out_h;
-    a.Wo = out_w;
-  }
-  a.cout = cout; a.nch = nch; a.epi = epi; a.dil = dil;
-  if (red) {
-    a.rraw = (const f16*)red->raw; a.ldrraw = red->ldraw; a.rcoef = red->coef; a.racc = red->acc; a.rC = red->C;
-    a.res = (const f16*)red->res; a.ldres = red->ldres;
-    if (red->xs) a.xs = *red->xs;
-    if (red->ys) a.ys = *red->ys;
-  }
+  a.Ho = p.Ho; a.Wo = p.Wo; a.npix = p.npix; a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y;
+  a.cout = cout; a.nch = p.nch; a.epi = epi; a.dil = dil;
+  a.rraw = (const f16*)red.raw; a.ldrraw = red.ldraw; a.rcoef = red.coef; a.racc = red.acc; a.rC = red.C;
+  a.res = (const f16*)red.res; a.ldres = red.ldres;
+  if (red.xs) a.xs = *red.xs;
+  if (red.ys) a.ys = *red.ys;
   static const bool xcd_map = getenv("DY_CONV_NO_XCDMAP") == nullptr;
   a.xcd_map = xcd_map && ks == 3;  // 1x1 tiles have no halo to share
-  int gx;
-  if (ks == 1) {
-    a.npix = n * a.Ho * a.Wo;
-    gx = cdiv(a.npix, 256);
-  } else {
-    const int th = stride == 1 ? 8 : 4;
-    a.tiles_x = cdiv(a.Wo, 32);
-    a.tiles_y = cdiv(a.Ho, th);
-    gx = a.tiles_x * a.tiles_y * n;
-  }
-  if (num_partials) *num_partials = dy_conv_num_partials(n, h, w, cin, cout, ks, stride, dil);
-  if ((epi & DY_EPI_STATS) && !partials) return DY_ERR_ARG;
-  if (gx <= 0) return DY_ERR_ARG;
-  if (dil == 2 && !g_no_dg2 && !g_force_v1 && (cc == 32 || cc == 64) && !(epi & ~DY_EPI_ACCUM) && !((uintptr_t)y & 15) && !(ldy & 7) &&
-      cout % 8 == 0 && dg2_lds_bytes(cc, mt, nch) <= DY_WLDS_BUDGET && (double)h * w * ldx * 2.0 < 2147483648.0) {
-#define DY_DG2(C, M) if (cc == C && mt == M) return launch_dg2<C, M>(a, ng, stream);
+  if (p.fam == CONV_DG2) {
+#define DY_DG2(C, M) if (p.cc == C && p.g.mt == M) return launch_planned<conv_mfma_dg2_kernel<C, M>>(a, p, stream);
     DY_DG2(32, 1) DY_DG2(32, 2) DY_DG2(32, 4) DY_DG2(64, 1) DY_DG2(64, 2) DY_DG2(64, 4)
 #undef DY_DG2
+    return DY_ERR_ARG;
   }
-  if (ks == 1 && !(red && (red->raw || red->res)) && !(ldy & 7) && !((uintptr_t)y & 15) &&
-      conv1x1_stream_wanted(cin, cout, a.npix, epi, segx ? red->xs : nullptr, segy ? red->ys : nullptr)) {
-    Conv1x1StreamArgs sa{};
-    int nks, smt, sng, cpk;
-    if (!conv1x1_stream_shape(cin, cout, &nks, &smt, &sng, &cpk)) return DY_ERR_ARG;
-    sa.w = a.w; sa.y = y; sa.acc = reinterpret_cast<double*>(partials); sa.ldy = ldy; sa.npix = a.npix; sa.cout = cout; sa.epi = epi;
-    sa.cpk = cpk; sa.N = n; sa.H = h; sa.W = w;
-    if (segx) {
-      sa.xs = *red->xs;
-    } else {  // a plain tensor is one segment
-      sa.xs.nseg = 1; sa.xs.c_end[0] = cin; sa.xs.ld[0] = ldx; sa.xs.acc[0] = 0; sa.xs.ptr[0] = x;
-    }
-    if (segy) sa.ys = *red->ys;
-    if (epi & DY_EPI_STATS) sa.pp_grid = pp_grid(cc, mt, 1, 1, nch, 2, cdiv(a.npix, 256));  // cc, nch: what the ping-pong launch would use
-    return conv1x1_stream_launch(sa, nks, smt, sng, stream);
-  }
-  if (ks == 1) return dispatch_cc_mt<1, 1, 2>(cc, mt, a, gx, ng, stream);
-  if (stride == 1) return dispatch_cc_mt<3, 1, 2>(cc, mt, a, gx, ng, stream);
-  return dispatch_cc_mt<3, 2, 1>(cc, mt, a, gx, ng, stream);
+  if (ks == 1) return dispatch_cc_mt<1, 1>(a, p, stream);
+  if (stride == 1) return dispatch_cc_mt<3, 1>(a, p, stream);
+  return dispatch_cc_mt<3, 2>(a, p, stream);
 }
 
-// name of the kernel instantiation dy_conv_forward launches for a geometry, spelled as rocprofv3 prints it (host-side
-// helper: lets bench.py group its live per-launch timings by the same kernel names as the committed profiles)
+extern "C" int dy_conv_forward(const void* x, int ldx, const void* w_packed, const float* bias, void* y, int ldy,
+                               float* partials, int n, int h, int w, int cin, int cout, int ks, int stride, int dil,
+                               int out_h, int out_w, int epi, int* num_partials, hipStream_t stream) {
+  return conv_forward_impl(x, ldx, w_packed, bias, y, ldy, partials, n, h, w, cin, cout, ks, stride, dil, out_h, out_w, epi, num_partials,
+                           stream, RedHost{});
+}
+// 1 when dy_conv_input_grad_red can take this (stride-1) input-gradient geometry: the ping-pong kernel with its transposing epilogue
+extern "C" int dy_conv_red_supported(int cin, int cout, int ks) {
+  ConvQuery q = conv_query(cin, cout, ks, 1, 0);
+  q.red = true;
+  return conv_plan(q).err == DY_OK;
+}
+// dy_conv_forward over the transposed pack, with the first pass of the consumer's BatchNorm backward in the epilogue (dealyolo_hip.h)
+extern "C" int dy_conv_input_grad_red(const void* dy, int lddy, const void* w_packed_t, void* dx, int lddx, int n, int h, int w, int cin,
+                                      int cout, int ks, const void* raw, int ldraw, const float* coef, double* acc, int C,
+                                      hipStream_t stream) {
+  if (!raw || !coef || !acc || C != cout || (ldraw & 7) || ((uintptr_t)raw & 15) || (lddx & 7)) return DY_ERR_ARG;
+  const RedHost red{raw, ldraw, coef, acc, C, nullptr, 0, nullptr, nullptr};
+  return conv_forward_impl(dy, lddy, w_packed_t, nullptr, dx, lddx, nullptr, n, h, w, cin, cout, ks, 1, 1, 0, 0, 0, nullptr, stream, red);
+}
+// 1 when dy_conv_forward_res can take this geometry: the ping-pong kernel's transposing epilogue (whole 8-channel pieces)
+extern "C" int dy_conv_res_supported(int cin, int cout, int ks, int stride) {
+  ConvQuery q = conv_query(cin, cout, ks, stride, 0);
+  q.res = true;
+  return conv_plan(q).err == DY_OK;
+}
+// y = fp16(fp16(SiLU(conv(x) + bias)) + res): Conv.forward_fuse and Bottleneck's shortcut add in one launch (dealyolo_hip.h)
+extern "C" int dy_conv_forward_res(const void* x, int ldx, const void* w_packed, const float* bias, const void* res, int ldres, void* y,
+                                   int ldy, int n, int h, int w, int cin, int cout, int ks, int stride, hipStream_t stream) {
+  if (!res || !bias || (ldres & 7) || ((uintptr_t)res & 15) || (ldy & 7)) return DY_ERR_ARG;
+  const RedHost red{nullptr, 0, nullptr, nullptr, 0, res, ldres, nullptr, nullptr};
+  return conv_forward_impl(x, ldx, w_packed, bias, y, ldy, nullptr, n, h, w, cin, cout, ks, stride, 1, 0, 0,
+                           DY_EPI_BIAS | DY_EPI_SILU | DY_EPI_RES, nullptr, stream, red);
+}
+// ---- 1x1 convolutions over a never-materialised concatenation (DySegs)
+extern "C" int dy_segs_bytes(void) { return (int)sizeof(DySegs); }
+static ConvQuery segs_query(int cin, int cout, const DySegs* xs, int ask) {
+  static const DySegs none{};  // (a null table is an invalid one, not a plain input)
+  ConvQuery q = conv_query(cin, cout, 1, 1, ask);
+  q.xs = xs ? xs : &none;
+  return q;
+}
+extern "C" int dy_conv1x1_segs_supported(int cin, int cout, const DySegs* xs) { return conv_plan(segs_query(cin, cout, xs, 0)).err == DY_OK; }
+// the instantiation dy_conv1x1_forward_segs launches for these segments where the stream kernel does not take the launch
+extern "C" int dy_conv1x1_segs_kernel_name(int cin, int cout, const DySegs* xs, char* out, int cap) {
+  const ConvQuery q = segs_query(cin, cout, xs, 0);
+  return plan_name(conv_plan(q), q, out, cap);
+}
+// dy_conv_forward for a 1x1 convolution whose INPUT is the concatenation xs, without the cat (dealyolo_hip.h) ...
+extern "C" int dy_conv1x1_forward_segs(const DySegs* xs, const void* w_packed, const float* bias, void* y, int ldy, float* partials, int n,
+                                       int h, int w, int cin, int cout, int epi, hipStream_t stream) {
+  if (!xs) return DY_ERR_ARG;
+  const RedHost red{nullptr, 0, nullptr, nullptr, 0, nullptr, 0, xs, nullptr};
+  return conv_forward_impl(nullptr, 0, w_packed, bias, y, ldy, partials, n, h, w, cin, cout, 1, 1, 1, 0, 0, epi, nullptr, stream, red);
+}
+// ... and its input gradient, stored in or added to the concat members' gradient tensors segment by segment (dxs->acc)
+extern "C" int dy_conv1x1_input_grad_segs(const void* dy, int lddy, const void* w_packed_t, const DySegs* dxs, int n, int h, int w, int cin,
+                                          int cout, hipStream_t stream) {
+  if (!dxs) return DY_ERR_ARG;
+  const RedHost red{nullptr, 0, nullptr, nullptr, 0, nullptr, 0, nullptr, dxs};
+  return conv_forward_impl(dy, lddy, w_packed_t, nullptr, nullptr, 0, nullptr, n, h, w, cin, cout, 1, 1, 1, 0, 0, 0, nullptr, stream, red);
+}
+
+// ---- planning helpers: each fills a plan for the question its contract asks and reads one field
+// Name of the ping-pong / v3 / v1 instantiation of a geometry, spelled as rocprofv3 prints it (lets bench.py group its live per-launch
+// timings by the same kernel names as the committed profiles).  It asks about the geometry alone, so it names that instantiation
+// even where full-width tiles, the stream kernel or dg2 would take the launch ("true" for REDK: dy_conv_input_grad_red).
 extern "C" int dy_conv_kernel_name(int cin, int cout, int ks, int stride, char* out, int cap) {
-  int cp, op, cc, nch, mt, ng, kst, pe;
-  if (!out || cap < 8 || dy_conv_geometry(cin, cout, ks, stride, &cp, &op, &cc, &nch, &mt, &ng, &kst, &pe) != DY_OK) return DY_ERR_ARG;
-  const int pp = pp_trows(cc, mt, ks, stride, nch);
-  if (pp) {
-    snprintf(out, cap, "conv_mfma_pp_kernel<%d, %d, %d, %d, %d, false, 0>", cc, mt, ks, stride, pp);  // "true": dy_conv_input_grad_red
-    return DY_OK;
-  }
-  const int cfg = (g_force_v1 || (cc == 64 && stride == 2)) ? 0 : v3_trows(cc, mt, ks, stride, nch);
-  if (cfg == 2 && !(ks == 3 && stride == 2)) snprintf(out, cap, "conv_mfma_wlds_kernel<%d, %d, %d, %d, 2, 8>", cc, mt, ks, stride);
-  else if (cfg == 4 && ks == 3 && stride == 1) snprintf(out, cap, "conv_mfma_wlds_kernel<%d, %d, %d, %d, 2, 4>", cc, mt, ks, stride);
-  else if (cfg == 1) snprintf(out, cap, "conv_mfma_wlds_kernel<%d, %d, %d, %d, 1, 8>", cc, mt, ks, stride);
-  else snprintf(out, cap, "conv_mfma_kernel<%d, %d, %d, %d, %d>", cc, mt, ks, stride, (ks == 3 && stride == 2) ? 1 : 2);
-  return DY_OK;
+  const ConvQuery q = conv_query(cin, cout, ks, stride, 0);
+  return plan_name(conv_plan(q), q, out, cap);
 }
-
-// name of the kernel a 1x1 launch REALLY runs (dy_conv_forward with ks = 1, dy_conv1x1_forward_segs with xs, dy_conv1x1_input_grad_segs
-// with ys): the stream kernel where conv1x1_stream_wanted selects it, else the ping-pong instantiation the helpers above name.
-// It sees the geometry, not the pointers: an output with ldy % 8 != 0 or a y that is not 16-byte aligned (legal for the ping-pong
-// kernel, never produced by the engine) also keeps a launch on the ping-pong kernel, and this function cannot know.
-extern "C" int dy_conv1x1_kernel_name_live(int cin, int cout, int n, int h, int w, int epi, const DySegs* xs, const DySegs* ys, char* out,
-                                           int cap) {
-  if (!out || cap < 8) return DY_ERR_ARG;
-  if ((double)n * h * w < 2147483648.0 && conv1x1_stream_wanted(cin, cout, n * h * w, epi, xs, ys)) {
-    int nks, mt, ng, cpk;
-    if (!conv1x1_stream_shape(cin, cout, &nks, &mt, &ng, &cpk)) return DY_ERR_ARG;
-    snprintf(out, cap, "conv1x1_stream_kernel<%d, %d, %s>", nks, mt, (epi & DY_EPI_STATS) ? "true" : "false");
-    return DY_OK;
-  }
-  if (xs) return dy_conv1x1_segs_kernel_name(cin, cout, xs, out, cap);
-  return dy_conv_kernel_name(cin, cout, 1, 1, out, cap);
-}
-
 // ... for a given output width and epilogue: maps exactly 40 (80) pixels wide take the full-width tiles of conv_mfma_pp_kernel (last
 // template argument), whose launches rocprofv3 lists as a kernel of their own
 extern "C" int dy_conv_kernel_name_at(int cin, int cout, int ks, int stride, int out_w, int dil, int epi, char* out, int cap) {
-  const int rc = dy_conv_kernel_name(cin, cout, ks, stride, out, cap);
-  if (rc != DY_OK) return rc;
-  int cp, op, cc, nch, mt, ng, kst, pe;
-  dy_conv_geometry(cin, cout, ks, stride, &cp, &op, &cc, &nch, &mt, &ng, &kst, &pe);
-  const int pp = pp_trows(cc, mt, ks, stride, nch);
-  const int fw = pp ? pp_fw_for(cc, mt, ks, stride, nch, out_w, dil, epi, false) : 0;
-  if (fw) snprintf(out, cap, "conv_mfma_pp_kernel<%d, %d, %d, %d, %d, false, %d>", cc, mt, ks, stride, 80 / fw, fw);
-  return DY_OK;
+  ConvQuery q = conv_query(cin, cout, ks, stride, ASK_FW);
+  q.w = out_w; q.dil = dil; q.epi = epi;  // (q.h stays 0: a 3x3 stride-1 output is as tall as its input whatever the height)
+  return plan_name(conv_plan(q), q, out, cap);
 }
-
-// number of partial rows dy_conv_forward will write for a given problem (host-side planning helper)
+// Name of the kernel a 1x1 launch REALLY runs (dy_conv_forward with ks = 1, dy_conv1x1_forward_segs with xs, dy_conv1x1_input_grad_segs
+// with ys): the stream kernel where the plan selects it, else the ping-pong instantiation the helpers above name.  It sees the
+// geometry, not the pointers: an output with ldy % 8 != 0 or a y that is not 16-byte aligned (legal for the ping-pong kernel, never
+// produced by the engine) also keeps a launch on the ping-pong kernel, and this function cannot know.
+extern "C" int dy_conv1x1_kernel_name_live(int cin, int cout, int n, int h, int w, int epi, const DySegs* xs, const DySegs* ys, char* out,
+                                           int cap) {
+  ConvQuery q = conv_query(cin, cout, 1, 1, ASK_STREAM);
+  q.n = n; q.h = h; q.w = w; q.epi = epi; q.xs = xs; q.ys = ys; q.y_vec8 = true;
+  const ConvPlan p = conv_plan(q);
+  if (p.err == DY_OK && p.fam == CONV_STREAM) return plan_name(p, q, out, cap);
+  if (!out || cap < 8) return DY_ERR_ARG;
+  return xs ? dy_conv1x1_segs_kernel_name(cin, cout, xs, out, cap) : dy_conv_kernel_name(cin, cout, 1, 1, out, cap);
+}
+// number of partial rows dy_conv_forward will write for a given problem
 extern "C" int dy_conv_num_partials(int n, int h, int w, int cin, int cout, int ks, int stride, int dil) {
-  const int H = dil == 2 ? 2 * h : h, W = dil == 2 ? 2 * w : w, pad = ks / 2;
-  const int Ho = (H + 2 * pad - ks) / stride + 1, Wo = (W + 2 * pad - ks) / stride + 1;
-  int tiles;
-  if (ks == 1) tiles = cdiv(n * Ho * Wo, 256);
-  else tiles = cdiv(Wo, 32) * cdiv(Ho, stride == 1 ? 8 : 4) * n;
-  int cp, op, cc, nch, mt, ng, kst, pe;
-  if (dy_conv_geometry(cin, cout, ks, stride, &cp, &op, &cc, &nch, &mt, &ng, &kst, &pe) != DY_OK) return tiles;
-  if (const int pp = pp_trows(cc, mt, ks, stride, nch)) {
-    const int nt = ks == 1 ? cdiv(n * Ho * Wo, 4 * 2 * pp * 16) : cdiv(Wo, 32) * cdiv(Ho, 4 * pp) * n;
-    return pp_grid(cc, mt, ks, stride, nch, pp, nt);
-  }
-  const int cfg = (g_force_v1 || (cc == 64 && stride == 2)) ? 0 : v3_trows(cc, mt, ks, stride, nch);
-  if (!cfg) return tiles;
-  const int t3 = ks == 1 ? cdiv(n * Ho * Wo, v3_flat_pix(cfg)) : cdiv(Wo, 32) * cdiv(Ho, v3_tile_rows(cfg)) * n;
-  return t3 > DY_WLDS_MAX_WGS ? DY_WLDS_MAX_WGS : t3;
+  ConvQuery q = conv_query(cin, cout, ks, stride, 0);
+  q.n = n; q.h = h; q.w = w; q.dil = dil;
+  return conv_plan(q).partials;
 }

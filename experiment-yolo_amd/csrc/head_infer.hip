@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256, 2) void head_infer_kernel(HeadInferArgs g) {
   }
 }
 
-// channels per k-step and k-steps dy_conv_forward's geometry gives a 1x1 conv over cin channels (csrc/conv.hip pick_cc): whole
+// channels per k-step and k-steps dy_conv_forward's geometry gives a 1x1 conv over cin channels (csrc/conv.hip conv_geom): whole
 // 32-channel steps where cin is a multiple of 32, otherwise 16-channel chunks (one half-empty MFMA each)
 static bool head_infer_shape(int cin, int* cck, int* ks) {
   if (cin >= 32 && cin % 32 == 0 && cin <= 128) { *cck = 32; *ks = cin / 32; return true; }

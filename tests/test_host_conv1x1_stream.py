@@ -1,4 +1,4 @@
-"""Host side of the streaming 1x1 convolution (csrc/conv.hip conv1x1_stream_wanted, dy_conv1x1_kernel_name_live): which kernel a 1x1
+"""Host side of the streaming 1x1 convolution (csrc/conv.hip conv_plan, dy_conv1x1_kernel_name_live): which kernel a 1x1
 launch runs under DY_CONV1X1_STREAM = 0 / force / unset.  No GPU: the helpers only do arithmetic on the geometry."""
 import json
 import os
