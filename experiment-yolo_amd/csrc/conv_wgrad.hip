@@ -41,6 +41,12 @@ struct WgArgs {
   // plane 0 would read plane 1 -- the BN forms zero such granules by the RAW tensor's range check, which is why only they take planes.)
   int dy_csplit;
   unsigned dy_plane;
+  // BNF 5 / 7 (1x1, one Cout chunk): the input gradient dX = W^T d(raw) is formed from the d(raw) tile in LDS (see the kernel), draw is unused
+  const f16* wt;        // the transposed pack of the layer (dy_pack_weights, transposed = 1): [cout group][k-step][16 * dg_mt rows][32]
+  f16* dx;              // BNF 5: (npix, lddx) fp16, stored or (dx_acc) added to
+  int lddx, dx_acc;
+  int dg_mt, dg_rows;   // rows per cout group of that pack / 16, and all its rows
+  DySegs dxs;           // BNF 7: the members' gradient tensors, stored or added per member (dy_conv1x1_input_grad_segs)
 };
 
 static __device__ __forceinline__ half8 tr_frag(const char* base0, const char* base1) {
@@ -69,8 +75,10 @@ template <int KS, int STRIDE, int NCI, int MTC, int BNF>
 // channels over two workgroups to fit was measured slower, 258 vs 224 us.)
 __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void conv_wgrad_kernel(const WgArgs a) {
   constexpr bool FLAT = (KS == 1);
-  constexpr bool BN1 = (BNF == 1 || BNF == 3);   // BatchNorm + SiLU backward formed while staging dY
-  constexpr bool XSEG = (BNF == 3);              // ... and X is a segmented concatenation
+  constexpr bool DG = (BNF & 4) != 0;            // BNF 5 / 7 = 1 / 3 with the input gradient formed here as well (FLAT, one Cout chunk)
+  constexpr bool BN1 = ((BNF & 3) == 1 || (BNF & 3) == 3);   // BatchNorm + SiLU backward formed while staging dY
+  constexpr bool XSEG = ((BNF & 3) == 3);        // ... and X is a segmented concatenation
+  static_assert(!DG || (KS == 1 && BN1), "the fused input gradient exists for the 1x1 BatchNorm forms");
   constexpr int TAPS = KS * KS;
   constexpr int NCOL = NCI * TAPS;          // (ci tile, tap) columns of this workgroup
   constexpr int CPW = (NCOL + 3) / 4;       // columns per wave (round-robin)
@@ -93,6 +101,18 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
   __shared__ __attribute__((aligned(16))) float sbn[BN1 ? 4 * COUT_C : (BNF == 2 ? 256 * 8 : 4)];  // BNF 1: [sc | sh | kb | kc] of this cout chunk; 2: bias-sum scratch
   float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // BNF 2: sum over pixels of this thread's dY granule (its channel part is fixed)
   (void)bsum;
+  // ---- DG: dX[this Cin chunk][tile pixels] = W^T . d(raw), with the instruction, the orientation (M = Cin rows of the transposed pack,
+  // N = pixels) and the k order (the pack's k-steps, ascending, from zero) of conv1x1_stream_kernel and conv_mfma_pp_kernel's 1x1 branch,
+  // so every dX element is the same MFMA chain as in the two-launch form.  The pack's k-steps for this many d(raw) channels (conv_geom
+  // of the transposed layer): 16 -> 1 step of 16 real channels, 32 -> 1, 48 -> 3 of 16 real channels, 64 -> 2.
+  constexpr int DKS = MTC == 4 ? 2 : (MTC == 3 ? 3 : 1), DCPK = (MTC & 1) ? 16 : 32;
+  constexpr int DNT = TH / 2;               // 16-pixel N-tiles per wave: wave w owns pixels [w * 16 DNT, (w + 1) * 16 DNT) of the tile
+  constexpr int DNC = 4 * NCI;              // consecutive dX channels a lane holds per pixel (row map below)
+  constexpr int DXROW = CIN_C * 2 + 16;     // pitch of the per-wave store-transpose scratch (16 pixel rows)
+  constexpr int DPPR = CIN_C / 8;           // 16-byte pieces per pixel
+  constexpr int DPIXPASS = 64 / DPPR > 16 ? 16 : 64 / DPPR;  // pixels one store instruction covers
+  constexpr int DNPASS = (16 + DPIXPASS - 1) / DPIXPASS;
+  __shared__ __attribute__((aligned(16))) char sdx[DG ? 4 * 16 * DXROW : 16];
 
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, p = lane & 15, q = lane >> 4;
   const int qq = p >> 2, pp = p & 3;  // address-supplier role inside the 16-lane group
@@ -194,6 +214,57 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
     }
     __syncthreads();
   }
+  // DG: A fragments (W^T rows of this Cin chunk) resident in registers.  Row i of M-tile j is channel ci0 + (i >> 2) * DNC + 4 j + (i & 3),
+  // so that a lane's accumulators of the NCI tiles are DNC consecutive channels of one pixel; where that row sits in the pack follows
+  // pack_one (conv.hip): group = ch / (16 mt), row = tile * 16 + quad * 4 + r with ch % (16 mt) = quad * 4 mt + tile * 4 + r.
+  half8 wf[DG ? DKS : 1][DG ? NCI : 1];
+  unsigned dboff[DG ? DKS : 1];       // byte offset of this lane's 8 channels of k-step k inside a staged d(raw) pixel
+  char* dxb = nullptr;                // this lane's store piece: base pointer at its channel (null: absent channels) ...
+  unsigned dxld2 = 0;                 // ... and the pixel stride in bytes
+  bool dxacc = false, dxadd = false;  // this lane's piece accumulates / (kernel-uniform) the epilogue adds old values
+  const int dpix = lane / DPPR, dpiece = lane - dpix * DPPR;
+  (void)wf; (void)dboff; (void)dxb; (void)dxld2; (void)dxacc; (void)dxadd; (void)dpix; (void)dpiece;
+  if (DG) {
+#pragma unroll
+    for (int k = 0; k < DKS; ++k) {
+      dboff[DG ? k : 0] = (unsigned)((k * DCPK + ((q * 8) & (DCPK - 1))) * 2);  // (16-channel steps: lanes q >= 2 meet zero weights)
+#pragma unroll
+      for (int j = 0; j < NCI; ++j) {
+        const int ch = ci0 + (p >> 2) * DNC + 4 * j + (p & 3);
+        const int gw = 16 * a.dg_mt, g = ch / gw, rem = ch - g * gw;
+        const int row = g * gw + ((rem % (4 * a.dg_mt)) >> 2) * 16 + (rem / (4 * a.dg_mt)) * 4 + (rem & 3);
+        const int grow = (g * DKS + k) * gw + (row - g * gw);
+        half8 v;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (f16)0.f;
+        if (row < a.dg_rows) v = *reinterpret_cast<const half8*>(a.wt + ((size_t)grow * 32 + q * 8));
+        wf[DG ? k : 0][DG ? j : 0] = v;
+      }
+    }
+    const int chn = ci0 + dpiece * 8;  // first channel of this lane's stores
+    if (lane < DPIXPASS * DPPR && chn < a.cin_r8) {
+      if (XSEG) {
+        int sg = 0;
+        while (sg + 1 < a.dxs.nseg && chn >= a.dxs.c_end[sg]) ++sg;
+        const int cb = sg ? a.dxs.c_end[sg - 1] : 0;
+        dxb = reinterpret_cast<char*>(const_cast<void*>(a.dxs.ptr[sg])) + (chn - cb) * 2;
+        dxld2 = (unsigned)a.dxs.ld[sg] * 2u;
+        dxacc = a.dxs.acc[sg] != 0;
+      } else {
+        dxb = reinterpret_cast<char*>(a.dx) + chn * 2;
+        dxld2 = (unsigned)a.lddx * 2u;
+        dxacc = a.dx_acc != 0;
+      }
+    }
+    if (XSEG) {
+      for (int k = 0; k < a.dxs.nseg; ++k) dxadd = dxadd || a.dxs.acc[k] != 0;  // (a table with one adding member adds zeros elsewhere, as the two-launch form does)
+    } else {
+      dxadd = a.dx_acc != 0;
+    }
+  }
+  union DU4 { uint4 u; half2_ h[4]; };
+  DU4 dold[DG ? DNT : 1][DG ? DNPASS : 1];  // DG, accumulating: what dX holds, requested before the tile's MFMAs
+  (void)dold;
   auto ld16 = [](__amdgpu_buffer_rsrc_t r, unsigned off) {
     const auto v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)off, 0, 0);
     return *reinterpret_cast<const uint4*>(&v);
@@ -328,7 +399,7 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
                                          cf + COUT_C, cf + 2 * COUT_C, cf + 3 * COUT_C);
         if (!valid) o.u = make_uint4(0, 0, 0, 0);
         if (id < NGY) *reinterpret_cast<uint4*>(sy + (id / (COUT_C / 8)) * PSY + (id % (COUT_C / 8)) * 16) = o.u;
-        if (ci_chunk == 0 && a.draw) __builtin_amdgcn_raw_buffer_store_b128(o.v, rd, (int)(valid ? roff[i] + orcur : NEVER), 0, 0);
+        if (!DG && ci_chunk == 0 && a.draw) __builtin_amdgcn_raw_buffer_store_b128(o.v, rd, (int)(valid ? roff[i] + orcur : NEVER), 0, 0);
       }
     } else {
 #pragma unroll
@@ -343,6 +414,20 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
       }
     }
     __syncthreads();
+    const long dpix0 = (long)tile * (TH * TW) + wave * (16 * DNT);  // DG: first pixel of this wave's share of the tile
+    (void)dpix0;
+    if (DG && dxadd) {  // in front of the prefetch: the loads return in order, and the epilogue must not wait for the next tile's
+#pragma unroll
+      for (int t = 0; t < DNT; ++t)
+#pragma unroll
+        for (int ps = 0; ps < DNPASS; ++ps) {
+          const int rowi = ps * DPIXPASS + dpix;
+          const long gp = dpix0 + t * 16 + rowi;
+          const bool ok = dxb && dxacc && rowi < 16 && gp < a.npix;
+          dold[DG ? t : 0][DG ? ps : 0].u = ok ? *reinterpret_cast<const uint4*>(dxb + (size_t)gp * dxld2) : make_uint4(0, 0, 0, 0);
+        }
+      __builtin_amdgcn_sched_barrier(0);
+    }
     if (tile + (int)gridDim.x < a.ntiles) prefetch(tile + gridDim.x);
     // software-pipelined: A fragments of k-step r+1 and the B fragment of column c+1 are requested before the MFMAs
     // of (r, c) issue, so the transposed LDS reads run under the matrix pipe instead of in front of it
@@ -391,6 +476,68 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
             acc[m][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[r & 1][m], bf[lin & 1], acc[m][c], 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if (DG) {
+      // B fragments straight from the staged d(raw) tile: lane (p, q) reads pixel p, channels 32 k + 8 q .. + 7 (ds_read_b128; PSY in
+      // dwords is 8 mod 16, which also spreads the four 16-lane groups of a b128 read over all 64 banks)
+      half8 db[DNT][DKS];
+#pragma unroll
+      for (int t = 0; t < DNT; ++t)
+#pragma unroll
+        for (int k = 0; k < DKS; ++k)
+          db[t][k] = *reinterpret_cast<const half8*>(sy + ((wave * DNT + t) * 16 + p) * PSY + dboff[DG ? k : 0]);
+      f32x4 dacc[NCI][DNT];
+#pragma unroll
+      for (int j = 0; j < NCI; ++j)
+#pragma unroll
+        for (int t = 0; t < DNT; ++t) dacc[j][t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int k = 0; k < DKS; ++k)
+#pragma unroll
+        for (int j = 0; j < NCI; ++j)
+#pragma unroll
+          for (int t = 0; t < DNT; ++t)
+            dacc[j][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[DG ? k : 0][DG ? j : 0], db[t][k], dacc[j][t], 0, 0, 0);
+      // way out: the per-wave LDS transpose of the stream kernel's epilogue (a wave's LDS operations stay in order; the fences keep the
+      // compiler from reordering them), then 16-byte pieces -- consecutive lanes write one pixel's channels of this chunk
+      typedef uint2 __attribute__((may_alias)) uint2_a;
+      typedef uint4 __attribute__((may_alias)) uint4_a;
+      char* const xs = sdx + wave * (16 * DXROW);
+      char* const xw = xs + p * DXROW + q * (DNC * 2);
+      const int rrow = dpix < 16 ? dpix : 15;
+      auto lds_order = []() {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+      };
+#pragma unroll
+      for (int t = 0; t < DNT; ++t) {
+        union { half2_ h[DNC / 2]; uint2 u2[DNC / 4]; } hv;
+#pragma unroll
+        for (int j = 0; j < NCI; ++j) {
+          const f32x2 lo = {dacc[j][t][0], dacc[j][t][1]}, hi = {dacc[j][t][2], dacc[j][t][3]};
+          hv.h[j * 2] = __builtin_convertvector(lo, half2_);
+          hv.h[j * 2 + 1] = __builtin_convertvector(hi, half2_);
+        }
+        lds_order();  // the previous N-tile's reads are done
+#pragma unroll
+        for (int j = 0; j < NCI; ++j) reinterpret_cast<uint2_a*>(xw)[j] = hv.u2[j];
+        lds_order();
+#pragma unroll
+        for (int ps = 0; ps < DNPASS; ++ps) {
+          const int rowi = ps * DPIXPASS + dpix;
+          const int rr = ps * DPIXPASS + rrow < 16 ? ps * DPIXPASS + rrow : 15;
+          DU4 v;
+          v.u = *reinterpret_cast<const uint4_a*>(xs + rr * DXROW + dpiece * 16);
+          const long gp = dpix0 + t * 16 + rowi;
+          if (dxadd) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              v.h[k] = __builtin_convertvector(__builtin_convertvector(v.h[k], f32x2) + __builtin_convertvector(dold[DG ? t : 0][DG ? ps : 0].h[k], f32x2), half2_);
+          }
+          if (dxb && rowi < 16 && gp < a.npix) *reinterpret_cast<uint4*>(dxb + (size_t)gp * dxld2) = v.u;
+        }
       }
     }
   }
@@ -531,7 +678,13 @@ extern "C" int dy_wgrad_reduce_batched(const void* descs_device, int n, int tota
 
 template <int KS, int STRIDE, int NCI, int MTC>
 static int launch_wgrad(const WgArgs& a, int gx, int gy, hipStream_t s) {
-  if (a.raw && a.xs.nseg > 0) {
+  if (a.wt) {  // the fused input gradient: 1x1 BatchNorm forms whose one Cout chunk is the whole layer (dy_conv1x1_wgrad_dgrad_supported)
+    if constexpr (KS == 1) {
+      if (!a.raw || gy != a.nci_chunks) return DY_ERR_ARG;
+      if (a.xs.nseg > 0) hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 7>), dim3(gx, gy), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 5>), dim3(gx, gy), dim3(256), 0, s, a);
+    } else return DY_ERR_ARG;
+  } else if (a.raw && a.xs.nseg > 0) {
     if constexpr (KS == 1) hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 3>), dim3(gx, gy), dim3(256), 0, s, a);
     else return DY_ERR_ARG;
   } else if (a.raw) hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 1>), dim3(gx, gy), dim3(256), 0, s, a);
@@ -630,6 +783,8 @@ struct WgBnHost {  // BatchNorm + SiLU backward folded into the staging of dY (d
   const DySegs* xs = nullptr;  // dy_conv1x1_wgrad_bn_segs: the X operand is a segmented concatenation
   int dy_csplit = 0;           // dy_conv1x1_wgrad_bn_planes: dY in two planes (WgArgs)
   unsigned dy_plane = 0;
+  // dy_conv1x1_wgrad_dgrad_*: the input gradient from the same launch (WgArgs)
+  const void* wt = nullptr; void* dx = nullptr; int lddx = 0, dx_acc = 0; const DySegs* dxs = nullptr;
 };
 static int conv_wgrad_impl(const void* x, int ldx, const void* dy, int lddy, float* slabs, float* dw, int n, int h, int w,
                            int cin, int cout, int ks, int stride, int accumulate, int ld_taps, int ld_cphys, int ld_cin,
@@ -722,6 +877,94 @@ extern "C" int dy_conv1x1_wgrad_bn_planes(const DySegs* xs, const void* x, int l
   bn.dy_csplit = csplit; bn.dy_plane = (unsigned)plane;
   return conv_wgrad_impl(xs ? xs->ptr[0] : x, xs ? 8 : ldx, dy, lddy, slabs, dw, n, h, w, cin, cout, 1, 1, accumulate, 0, 0, 0, stream, &bn);
 }
+
+// ---- weight gradient + input gradient of a 1x1 Conv + BatchNorm + SiLU in one launch (conv_wgrad_kernel, BNF 5 / 7).  d(raw) exists in
+// the kernel's LDS tile only; the layer's output channels must all sit in ONE workgroup's block, so that no dX sum is split over workgroups.
+struct WgDgPlan { int ok, nci, mtc, dg_mt, dg_rows; };
+static WgDgPlan wgrad_dgrad_plan(int n, int h, int w, int cin, int cout) {
+  WgDgPlan r{};
+  if (n < 1 || h < 1 || w < 1 || cin < 8 || (cin & 7) || cout < 16 || (cout & 15) || cout > 64) return r;
+  int cp, op, nci, mtc;
+  wgrad_geometry(cin, cout, 1, 1, &cp, &op, &nci, &mtc, (long)n * h * w);
+  if (16 * mtc != op) return r;  // a small map split the Cout side over workgroups: two launches
+  // the transposed pack must be the one the kernel's k-steps assume (conv_wgrad_kernel, DKS / DCPK)
+  int gcin, gcout, cc, nch, mt, ng, kst, pe;
+  if (dy_conv_geometry(cout, cin, 1, 1, &gcin, &gcout, &cc, &nch, &mt, &ng, &kst, &pe) != DY_OK) return r;
+  const int dks = mtc == 4 ? 2 : (mtc == 3 ? 3 : 1), dcpk = (mtc & 1) ? 16 : 32;
+  if (gcin != cout || nch * kst != dks || (cc < 32 ? cc : 32) != dcpk || gcout < cp) return r;
+  r.ok = 1; r.nci = nci; r.mtc = mtc; r.dg_mt = mt; r.dg_rows = gcout;
+  return r;
+}
+extern "C" int dy_conv1x1_wgrad_dgrad_supported(int n, int h, int w, int cin, int cout) { return wgrad_dgrad_plan(n, h, w, cin, cout).ok; }
+// the instantiation the fused launch runs, spelled as rocprofv3 prints it (segs: the X operand / dX target is a DySegs table)
+extern "C" int dy_wgrad_dgrad_kernel_name(int n, int h, int w, int cin, int cout, int segs, char* out, int cap) {
+  const WgDgPlan pl = wgrad_dgrad_plan(n, h, w, cin, cout);
+  if (!out || cap < 8 || !pl.ok) return DY_ERR_ARG;
+  snprintf(out, cap, "conv_wgrad_kernel<1, 1, %d, %d, %d>", pl.nci, pl.mtc, segs ? 7 : 5);
+  return DY_OK;
+}
+static bool dgrad_segs_valid(const DySegs* xs, const DySegs* dxs) {
+  if (!xs || !dxs || dxs->nseg != xs->nseg) return false;
+  for (int k = 0; k < dxs->nseg; ++k) {
+    const int cb = k ? dxs->c_end[k - 1] : 0;
+    if (dxs->c_end[k] != xs->c_end[k] || (dxs->ld[k] & 7) || dxs->ld[k] < dxs->c_end[k] - cb || !dxs->ptr[k] || ((uintptr_t)dxs->ptr[k] & 15) ||
+        (dxs->acc[k] & ~1)) return false;
+  }
+  return true;
+}
+static bool segs_in_valid(const DySegs* xs, int cin, int h, int w) {
+  if (!xs || xs->nseg < 1 || xs->nseg > DY_MAX_SEGS || xs->c_end[xs->nseg - 1] != cin) return false;
+  for (int k = 0; k < xs->nseg; ++k)
+    if ((xs->c_end[k] & 7) || (xs->ld[k] & 7) || !xs->ptr[k] || ((uintptr_t)xs->ptr[k] & 15) || xs->c_end[k] <= (k ? xs->c_end[k - 1] : 0) ||
+        ((xs->acc[k] & 2) && ((h | w) & 1))) return false;
+  return true;
+}
+// dy_conv_wgrad_bn (ks 1) that also leaves dX = W^T d(raw) in (dx, lddx), stored or (dx_accumulate) added: no draw, no second launch
+extern "C" int dy_conv1x1_wgrad_dgrad_bn(const void* x, int ldx, const void* dy, int lddy, const void* raw, int ldraw, const float* coef,
+                                         const double* acc, float* dgamma, float* dbeta, float count, float* slabs, float* dw,
+                                         const void* w_packed_t, void* dx, int lddx, int dx_accumulate, int n, int h, int w, int cin,
+                                         int cout, int accumulate, hipStream_t stream) {
+  if (!raw || !coef || !acc || (ldraw & 7) || ((uintptr_t)raw & 15)) return DY_ERR_ARG;
+  if (!w_packed_t || ((uintptr_t)w_packed_t & 15) || !dx || ((uintptr_t)dx & 15) || (lddx & 7) || lddx < cin) return DY_ERR_ARG;
+  if (!wgrad_dgrad_plan(n, h, w, cin, cout).ok || (double)n * h * w * lddx * 2.0 >= 2147483648.0) return DY_ERR_ARG;
+  WgBnHost bn{raw, nullptr, coef, acc, dgamma, dbeta, ldraw, count};
+  bn.wt = w_packed_t; bn.dx = dx; bn.lddx = lddx; bn.dx_acc = dx_accumulate != 0;
+  return conv_wgrad_impl(x, ldx, dy, lddy, slabs, dw, n, h, w, cin, cout, 1, 1, accumulate, 0, 0, 0, stream, &bn);
+}
+// dy_conv1x1_wgrad_bn_segs with dy_conv1x1_input_grad_segs folded in: every 8-channel piece of dX goes to its member of dxs (the
+// members' gradient tensors: c_end as in xs, acc 1 = add), stored or added per member
+extern "C" int dy_conv1x1_wgrad_dgrad_bn_segs(const DySegs* xs, const void* dy, int lddy, const void* raw, int ldraw, const float* coef,
+                                              const double* acc, float* dgamma, float* dbeta, float count, float* slabs, float* dw,
+                                              const void* w_packed_t, const DySegs* dxs, int n, int h, int w, int cin, int cout,
+                                              int accumulate, hipStream_t stream) {
+  if (!raw || !coef || !acc || (ldraw & 7) || ((uintptr_t)raw & 15)) return DY_ERR_ARG;
+  if (!w_packed_t || ((uintptr_t)w_packed_t & 15) || !segs_in_valid(xs, cin, h, w) || !dgrad_segs_valid(xs, dxs)) return DY_ERR_ARG;
+  if (!wgrad_dgrad_plan(n, h, w, cin, cout).ok) return DY_ERR_ARG;
+  WgBnHost bn{raw, nullptr, coef, acc, dgamma, dbeta, ldraw, count};
+  bn.xs = xs; bn.wt = w_packed_t; bn.dxs = dxs;
+  return conv_wgrad_impl(xs->ptr[0], 8, dy, lddy, slabs, dw, n, h, w, cin, cout, 1, 1, accumulate, 0, 0, 0, stream, &bn);
+}
+// dy_conv1x1_wgrad_bn_planes likewise: xs / dxs for a concatenated input (then x, dx are unused), else (x, ldx) and (dx, lddx, dx_accumulate)
+extern "C" int dy_conv1x1_wgrad_dgrad_bn_planes(const DySegs* xs, const void* x, int ldx, const void* dy, const void* dy2, int lddy, int csplit,
+                                                const void* raw, int ldraw, const float* coef, const double* acc, float* dgamma,
+                                                float* dbeta, float count, float* slabs, float* dw, const void* w_packed_t, void* dx,
+                                                int lddx, int dx_accumulate, const DySegs* dxs, int n, int h, int w, int cin, int cout,
+                                                int accumulate, hipStream_t stream) {
+  if (!raw || !coef || !acc || (ldraw & 7) || ((uintptr_t)raw & 15)) return DY_ERR_ARG;
+  if (!dy || !dy2 || (csplit & 7) || csplit <= 0 || csplit >= cout || ((uintptr_t)dy2 & 15)) return DY_ERR_ARG;
+  const long plane = (const char*)dy2 - (const char*)dy;
+  if (plane < (long)n * h * w * lddy * 2 || plane + (double)n * h * w * lddy * 2.0 >= 2147483648.0) return DY_ERR_ARG;
+  if (!w_packed_t || ((uintptr_t)w_packed_t & 15) || !wgrad_dgrad_plan(n, h, w, cin, cout).ok) return DY_ERR_ARG;
+  if (xs) {
+    if (!segs_in_valid(xs, cin, h, w) || !dgrad_segs_valid(xs, dxs)) return DY_ERR_ARG;
+  } else if (dxs || !dx || ((uintptr_t)dx & 15) || (lddx & 7) || lddx < cin || (double)n * h * w * lddx * 2.0 >= 2147483648.0) {
+    return DY_ERR_ARG;
+  }
+  WgBnHost bn{raw, nullptr, coef, acc, dgamma, dbeta, ldraw, count};
+  bn.xs = xs; bn.dy_csplit = csplit; bn.dy_plane = (unsigned)plane;
+  bn.wt = w_packed_t; bn.dxs = xs ? dxs : nullptr; bn.dx = xs ? nullptr : dx; bn.lddx = lddx; bn.dx_acc = dx_accumulate != 0;
+  return conv_wgrad_impl(xs ? xs->ptr[0] : x, xs ? 8 : ldx, dy, lddy, slabs, dw, n, h, w, cin, cout, 1, 1, accumulate, 0, 0, 0, stream, &bn);
+}
 extern "C" int dy_conv_wgrad_ld_bn(const void* x, int ldx, const void* dy, int lddy, const void* raw, int ldraw, void* draw,
                                    const float* coef, const double* acc, float* dgamma, float* dbeta, float count, float* slabs,
                                    float* dw, int n, int h, int w, int cout, int ld_cin, int ld_taps, int ld_cphys, int accumulate,
@@ -757,6 +1000,13 @@ static int conv_wgrad_impl(const void* x, int ldx, const void* dy, int lddy, flo
     a.cout = bn->raw ? cout : (cout + 7) / 8 * 8;  // bias sums: one slot per physical channel of dY
     if (bn->xs) a.xs = *bn->xs;
     a.dy_csplit = bn->dy_csplit; a.dy_plane = bn->dy_plane;
+    if (bn->wt) {
+      const WgDgPlan pl = wgrad_dgrad_plan(n, h, w, cin, cout);
+      if (!pl.ok || pl.nci != nci || pl.mtc != mtc || ks != 1 || ld_taps) return DY_ERR_ARG;
+      a.wt = (const f16*)bn->wt; a.dx = (f16*)bn->dx; a.lddx = bn->lddx; a.dx_acc = bn->dx_acc;
+      a.dg_mt = pl.dg_mt; a.dg_rows = pl.dg_rows;
+      if (bn->dxs) a.dxs = *bn->dxs;
+    }
   }
   a.nci_chunks = cp / (16 * nci);
   const int nco_chunks = op / (16 * mtc);

@@ -136,6 +136,13 @@ SIGNATURES = {
     "dy_bn_act_bwd_reduce_acc_split": (i32, [vp, i32, vp, i32, i32, vp, i32, vp, vp, i64, i32, i32, vp]),
     "dy_conv1x1_wgrad_bn_planes": (i32, [C.POINTER(DySegs), vp, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, f32, vp, vp, i32, i32, i32,
                                          i32, i32, i32, vp]),
+    "dy_conv1x1_wgrad_dgrad_supported": (i32, [i32, i32, i32, i32, i32]),
+    "dy_wgrad_dgrad_kernel_name": (i32, [i32, i32, i32, i32, i32, i32, C.c_char_p, i32]),
+    "dy_conv1x1_wgrad_dgrad_bn": (i32, [vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "dy_conv1x1_wgrad_dgrad_bn_segs": (i32, [C.POINTER(DySegs), vp, i32, vp, i32, vp, vp, vp, vp, f32, vp, vp, vp, C.POINTER(DySegs), i32, i32,
+                                             i32, i32, i32, i32, vp]),
+    "dy_conv1x1_wgrad_dgrad_bn_planes": (i32, [C.POINTER(DySegs), vp, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, i32, i32,
+                                               C.POINTER(DySegs), i32, i32, i32, i32, i32, i32, vp]),
     "dy_bn_act_apply_acc_group": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dy_bn_act_bwd_reduce_acc_group": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dy_bn_act_bwd_reduce_rows": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp]),

@@ -114,6 +114,9 @@ CONV_RES = os.environ.get("DY_CONV_RES", "1") != "0"
 PLANAR = os.environ.get("DY_PLANAR", "1") != "0"
 HEAD_APPLY = HEAD_DECODE and os.environ.get("DY_SILU_FAST", "1") != "0" and os.environ.get("DY_HEAD_APPLY", "1") != "0"
 BN_DGRED = BN_WGRAD and os.environ.get("DY_BN_DGRED", "0") != "0"
+# The input gradient of a 1x1 Conv formed by its weight-gradient kernel from the d(raw) tile it holds in LDS (csrc/conv_wgrad.hip, BNF 5 / 7):
+# no d(raw) round trip through HBM and no input-gradient launch where dy_conv1x1_wgrad_dgrad_supported says so.  0 = the two-launch list.
+WGRAD_DGRAD = BN_WGRAD and not BN_DGRED and os.environ.get("DY_WGRAD_DGRAD", "1") != "0"
 BN_DGRED_MAXC = int(os.environ.get("DY_BN_DGRED_MAXC", "64"))
 BN_DGRED_MAXPIX = int(os.environ.get("DY_BN_DGRED_MAXPIX", str(1 << 40)))  # ... and the map size (N*H*W): small maps are latency-bound
 
@@ -969,7 +972,9 @@ class Engine:
             npix = y0.npix
             self.call("dy_bn_act_bwd_reduce_acc_split", y0.gptr, y0.ld, y1.gptr, y1.ld, y0.C, raw.ptr, raw.ld, spec.coef.data_ptr(),
                       self._acc_ready(spec.acc_b), npix, spec.cout, spec.act)
-            if self.cur_sid:
+            if self._wgrad_dgrad_ok(spec, x):
+                draw = None  # the fused launch keeps d(raw) in LDS
+            elif self.cur_sid:
                 draw = self.transient((npix * spec.cout,), torch.float16)
                 self.hold(draw)
             else:
@@ -1015,7 +1020,10 @@ class Engine:
                       spec.bwdcoef.data_ptr(), spec.cout, float(npix), 0)
         side_small = bool(SIDE_SMALL and npix <= SIDE_SMALL and self.deferred_wgrad is not None and not self.cur_sid and not self.side_wgrad
                           and acc and isinstance(x, Act) and x.needs_grad and spec.ld is None)
-        if ((self.side_wgrad or side_small) and self.deferred_wgrad is not None) or self.cur_sid:
+        bn_wgrad = bool(acc and BN_WGRAD and spec.act == DY_ACT_SILU and not self.side_wgrad and not side_small and raw.ld == spec.cout)
+        if bn_wgrad and self._wgrad_dgrad_ok(spec, x):
+            draw = None  # the fused launch keeps d(raw) in LDS
+        elif ((self.side_wgrad or side_small) and self.deferred_wgrad is not None) or self.cur_sid:
             # the weight gradient reads this buffer on the side stream while the main stream moves on to the next layer (or this
             # layer's backward runs on a branch beside the main chain's): it cannot be the shared scratch
             draw = self.transient((npix * spec.cout,), torch.float16)
@@ -1034,6 +1042,17 @@ class Engine:
             self.call("dy_bn_act_bwd_apply", y.gptr, y.ld, raw.ptr, raw.ld, draw.data_ptr(), spec.cout, spec.coef.data_ptr(),
                       spec.bwdcoef.data_ptr(), npix, spec.cout, spec.act, 0)
         self._conv_bwd(spec, x, draw.data_ptr(), spec.cout, y.H, y.W, side_hint=side_small)
+
+    def _wgrad_dgrad_ok(self, spec, x):
+        """The backward of ``spec`` (a 1x1 Conv + BatchNorm + SiLU on the BatchNorm-in-the-weight-gradient path) over input ``x`` is ONE
+        launch: weight gradient and input gradient together (dy_conv1x1_wgrad_dgrad_*).  Side-stream and branch backward passes, LDConv
+        forms and inputs that need no gradient keep the two-launch list."""
+        if not (WGRAD_DGRAD and spec.ks == 1 and spec.stride == 1 and spec.ld is None and isinstance(x, (Act, SegAct)) and x.needs_grad
+                and not self.cur_sid and not self.side_wgrad and spec.cout == spec.cout_phys and spec.cin == spec.cin_phys):
+            return False
+        if isinstance(x, SegAct) and not all(q.needs_grad for q in x.parts):
+            return False
+        return bool(self.L.dy_conv1x1_wgrad_dgrad_supported(x.N, x.H, x.W, spec.cin, spec.cout))
 
     def _conv_bwd(self, spec, x, dy_ptr, lddy, Ho, Wo, accumulate_w=0, defer=True, bn=None, bias_acc=None, planes=None, side_hint=False):
         """weight gradient + input gradient of one convolution given d(raw output) (fp16, (N,Ho,Wo,lddy)).
@@ -1057,6 +1076,28 @@ class Engine:
         if side:
             self._side_used = True
             self.fork()
+        if bn is not None and bn[1] is None:  # fused (_wgrad_dgrad_ok): the input-gradient call's bookkeeping, then one launch for both
+            raw, _, coef, accb, gw, gb, cnt = bn
+            assert not side and self._wgrad_dgrad_ok(spec, x)
+            seg = isinstance(x, SegAct)
+            if seg:
+                accs = [q.grad_target() for q in x.parts]
+                dxs, dx = C.byref(self._segs(x, grad=True, acc=accs)), (0, 0, 0)
+            else:
+                acc = x.grad_target()
+                dxs, dx = None, (x.gptr, x.ld, int(acc))
+            tail = (x.N, x.H, x.W, spec.cin, spec.cout, accumulate_w)
+            wt = spec.wpack_t.data_ptr()
+            if planes is not None:
+                self.call("dy_conv1x1_wgrad_dgrad_bn_planes", C.byref(self._segs(x)) if seg else None, 0 if seg else x.ptr, 0 if seg else x.ld,
+                          dy_ptr, planes[0], lddy, planes[1], raw.ptr, raw.ld, coef, accb, gw, gb, cnt, slabs.data_ptr(), dw, wt, *dx, dxs, *tail)
+            elif seg:
+                self.call("dy_conv1x1_wgrad_dgrad_bn_segs", C.byref(self._segs(x)), dy_ptr, lddy, raw.ptr, raw.ld, coef, accb, gw, gb, cnt,
+                          slabs.data_ptr(), dw, wt, dxs, *tail)
+            else:
+                self.call("dy_conv1x1_wgrad_dgrad_bn", x.ptr, x.ld, dy_ptr, lddy, raw.ptr, raw.ld, coef, accb, gw, gb, cnt, slabs.data_ptr(), dw,
+                          wt, *dx, *tail)
+            return
         if planes is not None:  # dY in two planes (dy_ptr, planes[0]), split at channel planes[1]; x a tensor or a concatenation
             raw, draw, coef, accb, gw, gb, cnt = bn
             seg = isinstance(x, SegAct)

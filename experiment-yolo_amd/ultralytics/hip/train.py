@@ -743,15 +743,38 @@ class StepPlan:
         elif name in ("dy_conv1x1_wgrad_bn_segs", "dy_conv1x1_wgrad_bn_planes") and alg:  # + raw read and d(raw) written
             n, h, w, _cin, cout = args[13:18] if name.endswith("segs") else args[17:22]
             own = alg + 2 * n * h * w * ((cout + 7) // 8 * 8) * e
+        elif name in self._FUSED_BWD and alg:  # X, dY and raw read, dX written (+ the old dX where it is added to); no d(raw) at all
+            n, h, w, cin, cout, old = self._fused_bwd_shape(name, args)
+            own = n * h * w * (2 * cin + 2 * cout + old) * e
         elif name == "dy_bn_act_apply_acc_split":
             own = int(args[13]) * int(args[14]) * e * 2
         elif name == "dy_bn_act_bwd_reduce_acc_split":
             own = int(args[9]) * int(args[10]) * e * 2
         return key, alg, own
 
+    # weight gradient + input gradient of a 1x1 Conv in one launch (csrc/conv_wgrad.hip, BNF 5 / 7): where (n, h, w, cin, cout) start
+    _FUSED_BWD = {"dy_conv1x1_wgrad_dgrad_bn": 17, "dy_conv1x1_wgrad_dgrad_bn_segs": 14, "dy_conv1x1_wgrad_dgrad_bn_planes": 21}
+
+    def _fused_bwd_shape(self, name, args):
+        """(n, h, w, cin, cout, channels of dX that are read before they are written) of a fused 1x1 backward call."""
+        i = self._FUSED_BWD[name]
+        n, h, w, cin, cout = args[i:i + 5]
+        dxs = args[13] if name.endswith("segs") else (args[20] if name.endswith("planes") else None)
+        if dxs is not None:
+            t = dxs._obj
+            old = sum((t.c_end[k] - (t.c_end[k - 1] if k else 0)) for k in range(t.nseg) if t.acc[k])
+        else:
+            old = cin if args[16 if name.endswith("bn") else 19] else 0
+        return n, h, w, cin, cout, old
+
     def _kernel_alg(self, name, args):
         import ctypes as C
         L, buf = self.eng.L, C.create_string_buffer(128)
+        if name in self._FUSED_BWD:  # the algorithmic bytes of both passes it replaces (weight gradient; input gradient as its call counted)
+            n, h, w, cin, cout, old = self._fused_bwd_shape(name, args)
+            seg = name.endswith("segs") or (name.endswith("planes") and args[0] is not None)
+            if L.dy_wgrad_dgrad_kernel_name(n, h, w, cin, cout, int(seg), buf, 128) == 0:
+                return buf.value.decode(), n * h * w * (2 * (cin + cout) + (0 if seg else old)) * 2
         if name == "dy_conv_forward":
             n, h, w, cin, cout, ks, stride, dil = args[7:15]
             if dil == 2 and ks == 3:

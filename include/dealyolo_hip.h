@@ -164,6 +164,30 @@ int dy_conv1x1_wgrad_bn_planes(const DySegs* xs, const void* x, int ldx, const v
                                const void* raw, int ldraw, void* draw, const float* coef, const double* acc, float* dgamma,
                                float* dbeta, float count, float* slabs, float* dw, int n, int h, int w, int cin, int cout,
                                int accumulate, hipStream_t stream);
+/* Weight gradient AND input gradient of a 1x1 Conv + BatchNorm + SiLU in one launch: the fused counterparts of dy_conv_wgrad_bn (ks 1),
+ * dy_conv1x1_wgrad_bn_segs and dy_conv1x1_wgrad_bn_planes.  d(raw) is formed while dY is staged, as there, but is never written out:
+ * the workgroup multiplies its LDS tile by the rows of w_packed_t (dy_pack_weights, transposed = 1) that belong to its Cin chunk and
+ * stores dX = W^T d(raw) itself -- into (dx, lddx), stored or (dx_accumulate) added to what it holds, or piece by piece into the
+ * members of dxs (dy_conv1x1_input_grad_segs' table: c_end as in xs, acc 1 = add).  Every dX element is the MFMA chain of the
+ * two-launch form (dy_conv_forward over w_packed_t / dy_conv1x1_input_grad_segs) and has its bits.  Exists where one workgroup's
+ * block holds every output channel of the layer -- cout a multiple of 16 up to 64 that the map's weight-gradient geometry does not
+ * split, cin a multiple of 8: dy_conv1x1_wgrad_dgrad_supported (host-side, no GPU needed); anything else is DY_ERR_ARG.
+ * dy_wgrad_dgrad_kernel_name: the instantiation such a launch runs, as rocprofv3 prints it (segs != 0: the xs / dxs form). */
+int dy_conv1x1_wgrad_dgrad_supported(int n, int h, int w, int cin, int cout);
+int dy_wgrad_dgrad_kernel_name(int n, int h, int w, int cin, int cout, int segs, char* out, int cap);
+int dy_conv1x1_wgrad_dgrad_bn(const void* x, int ldx, const void* dy, int lddy, const void* raw, int ldraw, const float* coef,
+                              const double* acc, float* dgamma, float* dbeta, float count, float* slabs, float* dw,
+                              const void* w_packed_t, void* dx, int lddx, int dx_accumulate, int n, int h, int w, int cin, int cout,
+                              int accumulate, hipStream_t stream);
+int dy_conv1x1_wgrad_dgrad_bn_segs(const DySegs* xs, const void* dy, int lddy, const void* raw, int ldraw, const float* coef,
+                                   const double* acc, float* dgamma, float* dbeta, float count, float* slabs, float* dw,
+                                   const void* w_packed_t, const DySegs* dxs, int n, int h, int w, int cin, int cout, int accumulate,
+                                   hipStream_t stream);
+int dy_conv1x1_wgrad_dgrad_bn_planes(const DySegs* xs, const void* x, int ldx, const void* dy, const void* dy2, int lddy, int csplit,
+                                     const void* raw, int ldraw, const float* coef, const double* acc, float* dgamma, float* dbeta,
+                                     float count, float* slabs, float* dw, const void* w_packed_t, void* dx, int lddx,
+                                     int dx_accumulate, const DySegs* dxs, int n, int h, int w, int cin, int cout, int accumulate,
+                                     hipStream_t stream);
 /* The stem Conv(3 -> 16, k 3, s 2, p 1) of the model YAMLs (nn/modules/conv.py:41-55 as model.0) read straight from the image
  * batch the trainer hands the model (models/yolo/detect/train.py:57-59: fp32 NCHW, img * mul): no import pass, no padded copy.
  * dy_stem_forward writes the raw conv output (N,Ho,Wo,ldraw) fp16 and ADDS the BatchNorm sums into acc [DY_BN_COPIES][2][16]
