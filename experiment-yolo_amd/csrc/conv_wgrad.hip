@@ -47,6 +47,8 @@ struct WgArgs {
   int lddx, dx_acc;
   int dg_mt, dg_rows;   // rows per cout group of that pack / 16, and all its rows
   DySegs dxs;           // BNF 7: the members' gradient tensors, stored or added per member (dy_conv1x1_input_grad_segs)
+  // BNF 13 / 15 (= 5 / 7 of a layer whose parameters are frozen, dy_conv1x1_dgrad_bn): the input gradient ALONE.  x, xs, slabs, dgamma and
+  // dbeta are never touched; a table in dxs (BNF 15) describes the targets only.
 };
 
 static __device__ __forceinline__ half8 tr_frag(const char* base0, const char* base1) {
@@ -73,11 +75,20 @@ template <int KS, int STRIDE, int NCI, int MTC, int BNF>
 // multiply in lock-step -- 29 % MFMA utilisation.  With two resident workgroups one stages while the other multiplies.
 // (The 64x64-channel 3x3 case needs 144 accumulator registers and cannot: it keeps one workgroup per CU; splitting its input
 // channels over two workgroups to fit was measured slower, 258 vs 224 us.)
-__global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void conv_wgrad_kernel(const WgArgs a) {
+// BNF 13 / 15 (no X tile, no dW accumulators): what is left in LDS is the d(raw) tile (<= 24 KB), the coefficient table (<= 1 KB) and
+// the store-transpose scratch (<= 9 KB), 34 KB at most of the CU's 160 KB, and the accumulator file is gone, so the register budget is
+// what bounds residency: (256, 3) -- 170 registers per lane -- holds the widest instantiation (NCI 4, MTC 3: 168 VGPRs; 12 resident
+// weight fragments and 16 dX accumulators of 4 registers each) without scratch, while (256, 4) would cap every one at 128 and spill the
+// eight that need 137-168.  The compiler reports 100-168 VGPRs, no scratch and 3-4 waves per SIMD for all 32 instantiations
+// (profiles/r08_freeze.md); three workgroups per CU, one staging while two multiply / store, is what the grid is sized for
+// (dgrad_only_columns).
+__global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) ? 1 : 2)) void conv_wgrad_kernel(const WgArgs a) {
   constexpr bool FLAT = (KS == 1);
   constexpr bool DG = (BNF & 4) != 0;            // BNF 5 / 7 = 1 / 3 with the input gradient formed here as well (FLAT, one Cout chunk)
+  constexpr bool NOX = (BNF & 8) != 0;           // BNF 13 / 15 = 5 / 7 without the weight gradient: no X operand at all
+  static_assert(!NOX || DG, "the form without X exists for the fused input gradient only");
   constexpr bool BN1 = ((BNF & 3) == 1 || (BNF & 3) == 3);   // BatchNorm + SiLU backward formed while staging dY
-  constexpr bool XSEG = ((BNF & 3) == 3);        // ... and X is a segmented concatenation
+  constexpr bool XSEG = ((BNF & 3) == 3);        // ... and X is a segmented concatenation (NOX: the dX targets are)
   static_assert(!DG || (KS == 1 && BN1), "the fused input gradient exists for the 1x1 BatchNorm forms");
   constexpr int TAPS = KS * KS;
   constexpr int NCOL = NCI * TAPS;          // (ci tile, tap) columns of this workgroup
@@ -94,7 +105,7 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
   // (in dwords: unit-stride pitch = 8 mod 16 -> 16/32/48/64 channels take 8/24/24/40; stride-2 pitch = 4 mod 8 -> data + 4)
   constexpr int PSX = (STRIDE == 2) ? CIN_C * 2 + 16 : (((CIN_C / 2 + 7) / 16) * 16 + 8) * 4;
   constexpr int PSY = (((COUT_C / 2 + 7) / 16) * 16 + 8) * 4;
-  constexpr int XBYTES = HHX * HWX * PSX, YBYTES = TH * TW * PSY;
+  constexpr int XBYTES = NOX ? 0 : HHX * HWX * PSX, YBYTES = TH * TW * PSY;
   __shared__ __attribute__((aligned(16))) char smem[XBYTES + YBYTES];
   char* const sx = smem;
   char* const sy = smem + XBYTES;
@@ -119,16 +130,19 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
   const int co_chunk = blockIdx.y / a.nci_chunks, ci_chunk = blockIdx.y - co_chunk * a.nci_chunks;
   const int ci0 = ci_chunk * CIN_C, co0 = co_chunk * COUT_C;
 
-  f32x4 acc[MTC][CPW];
+  f32x4 acc[NOX ? 1 : MTC][NOX ? 1 : CPW];
+  if (!NOX) {
 #pragma unroll
-  for (int m = 0; m < MTC; ++m)
+    for (int m = 0; m < MTC; ++m)
 #pragma unroll
-    for (int c = 0; c < CPW; ++c) acc[m][c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      for (int c = 0; c < CPW; ++c) acc[NOX ? 0 : m][NOX ? 0 : c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  (void)acc;
 
   // ---- software pipeline: the next tile's X halo and dY tile are fetched into registers while the current tile is
   // multiplied (one workgroup keeps ~30-60 KB of loads in flight under its MFMAs instead of idling on them)
   constexpr int NGX = HHX * HWX * (CIN_C / 8), NGY = TH * TW * (COUT_C / 8);
-  constexpr int NPX = (NGX + 255) / 256, NPY = (NGY + 255) / 256;
+  constexpr int NPX = NOX ? 1 : (NGX + 255) / 256, NPY = (NGY + 255) / 256;
   uint4 pfx[NPX], pfy[NPY];
   uint4 pfr[BN1 ? NPY : 1];     // BNF: raw conv output granules beside the dy granules
   unsigned roff[BN1 ? NPY : 1]; // their byte offsets in the (raw / draw) geometry
@@ -141,22 +155,24 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
   constexpr unsigned NEVER = 0x80000000u;
   constexpr int CPGX = CIN_C / 8, CPGY = COUT_C / 8;
   unsigned xoff[NPX], yoff[NPY];
+  (void)pfx; (void)xoff;
 #pragma unroll
   for (int i = 0; i < NPX; ++i) {
     const int id = tid + i * 256;
     const int pixel = id / CPGX, part = id - pixel * CPGX;
-    const bool ok = id < NGX && ci0 + part * 8 < a.cin_r8;
+    const bool ok = !NOX && id < NGX && ci0 + part * 8 < a.cin_r8;
     const int hy = FLAT ? 0 : pixel / HWX, hx = FLAT ? pixel : pixel - hy * HWX;
     xoff[i] = ok ? (unsigned)(((hy * a.W + hx) * a.ldx + ci0 + part * 8) * 2) : NEVER;
   }
-  const char* xb[XSEG ? NPX : 1];  // XSEG: where this thread's granule i lives (its segment's base at the granule's channel) ...
-  int xl[XSEG ? NPX : 1];          // ... and that segment's pixel stride in bytes
+  constexpr bool XIN = XSEG && !NOX;  // the X operand is read through a segment table
+  const char* xb[XIN ? NPX : 1];  // XSEG: where this thread's granule i lives (its segment's base at the granule's channel) ...
+  int xl[XIN ? NPX : 1];          // ... and that segment's pixel stride in bytes
   unsigned xup = 0;                // ... bit i: granule i's segment is a 2x nearest up-sampling of a (N, H/2, W/2) tensor (DySegs.acc = 2)
   bool any_up = false;             // (kernel-uniform) some segment is
-  if (XSEG)
+  if (XIN)
     for (int k = 0; k < a.xs.nseg; ++k) any_up = any_up || (a.xs.acc[k] & 2);
   (void)xb; (void)xl; (void)xup; (void)any_up;
-  if (XSEG) {
+  if (XIN) {
 #pragma unroll
     for (int i = 0; i < NPX; ++i) {
       const int id = tid + i * 256;
@@ -165,8 +181,8 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
       while (sg + 1 < a.xs.nseg && ch >= a.xs.c_end[sg]) ++sg;
       const int cb = sg ? a.xs.c_end[sg - 1] : 0;
       const bool ok = id < NGX && ch < a.cin_r8;
-      xb[XSEG ? i : 0] = ok ? reinterpret_cast<const char*>(a.xs.ptr[sg]) + (ch - cb) * 2 : nullptr;
-      xl[XSEG ? i : 0] = a.xs.ld[sg] * 2;
+      xb[XIN ? i : 0] = ok ? reinterpret_cast<const char*>(a.xs.ptr[sg]) + (ch - cb) * 2 : nullptr;
+      xl[XIN ? i : 0] = a.xs.ld[sg] * 2;
       if (ok && (a.xs.acc[sg] & 2)) xup |= 1u << i;
     }
   }
@@ -202,7 +218,7 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
         const float mean = a.coef[2 * a.cout + ch], inv = a.coef[3 * a.cout + ch];
         kb = sc * inv * mgx;
         kc = sc * mg - kb * mean;
-        if (blockIdx.x == 0 && ci_chunk == 0) {
+        if (!NOX && blockIdx.x == 0 && ci_chunk == 0) {
           if (a.dbeta) a.dbeta[ch] = (float)s1;
           if (a.dgamma) a.dgamma[ch] = (float)s2;
         }
@@ -274,7 +290,9 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
       const auto rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.x), 0, (int)((unsigned)a.npix * (unsigned)a.ldx * 2u), 0x00020000);
       const auto ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16*>(a.dy), 0, (int)((unsigned)a.npix * (unsigned)a.lddy * 2u + (a.dy_csplit ? a.dy_plane : 0u)), 0x00020000);
       const unsigned ox = (unsigned)tile * (TH * TW) * a.ldx * 2u, oy = (unsigned)tile * (TH * TW) * a.lddy * 2u;
-      if (XSEG) {
+      if (NOX) {
+        // no X operand
+      } else if (XIN) {
         const long p0 = (long)tile * (TH * TW);
         // up-sampled members: pixel (n, y, x) of the concatenation reads (n, y >> 1, x >> 1) of the low-resolution tensor.  The tile's
         // first pixel is decomposed once (uniform integer divisions), a lane's pixel lies < TH * TW further: exact float divisions
@@ -297,8 +315,8 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
             const int yt = y0 + dy_, dn = (int)(((float)yt + 0.5f) * invH), y = yt - dn * a.H;
             gp = ((long)(n0 + dn) * (a.H >> 1) + (y >> 1)) * (a.W >> 1) + (x >> 1);
           }
-          const char* src = xb[XSEG ? i : 0];
-          pfx[i] = (src && inside) ? *reinterpret_cast<const uint4*>(src + gp * xl[XSEG ? i : 0]) : make_uint4(0, 0, 0, 0);
+          const char* src = xb[XIN ? i : 0];
+          pfx[i] = (src && inside) ? *reinterpret_cast<const uint4*>(src + gp * xl[XIN ? i : 0]) : make_uint4(0, 0, 0, 0);
         }
       } else {
 #pragma unroll
@@ -379,7 +397,7 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
 #pragma unroll
     for (int i = 0; i < NPX; ++i) {
       const int id = tid + i * 256;
-      if (id < NGX) *reinterpret_cast<uint4*>(sx + (id / (CIN_C / 8)) * PSX + (id % (CIN_C / 8)) * 16) = pfx[i];
+      if (!NOX && id < NGX) *reinterpret_cast<uint4*>(sx + (id / (CIN_C / 8)) * PSX + (id % (CIN_C / 8)) * 16) = pfx[i];
     }
     if (BN1) {
       vcur = vnext; orcur = ornext; ncur = nnext;
@@ -431,6 +449,7 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
     if (tile + (int)gridDim.x < a.ntiles) prefetch(tile + gridDim.x);
     // software-pipelined: A fragments of k-step r+1 and the B fragment of column c+1 are requested before the MFMAs
     // of (r, c) issue, so the transposed LDS reads run under the matrix pipe instead of in front of it
+    if constexpr (!NOX) {
     const int kpix = 4 * q + qq;  // first-read row of this lane inside a k-step; the second read is 16 rows further.  (Which of
                                   // the 32 pixels of a k-step a lane's k index means is free as long as A and B agree: with
                                   // rows 4q+qq one 32-lane group reads 8 CONSECUTIVE rows, which the pitch above makes conflict-free.)
@@ -473,11 +492,12 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
         if (wave + 4 * c < NCOL) {
 #pragma unroll
           for (int m = 0; m < MTC; ++m)
-            acc[m][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[r & 1][m], bf[lin & 1], acc[m][c], 0, 0, 0);
+            acc[NOX ? 0 : m][NOX ? 0 : c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[r & 1][m], bf[lin & 1], acc[NOX ? 0 : m][NOX ? 0 : c], 0, 0, 0);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
     }
+    }  // !NOX
     if (DG) {
       // B fragments straight from the staged d(raw) tile: lane (p, q) reads pixel p, channels 32 k + 8 q .. + 7 (ds_read_b128; PSY in
       // dwords is 8 mod 16, which also spreads the four 16-lane groups of a b128 read over all 64 banks)
@@ -554,6 +574,7 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
       unsafeAtomicAdd(const_cast<double*>(a.acc) + (size_t)(blockIdx.x % DY_BN_COPIES) * a.cout + co0 + tid, (double)t);
     }
   }
+  if constexpr (NOX) return;  // no weight gradient: no slab
   // ---- one slab per workgroup: [tap][cout_p][cin_p] fp32 (16 lanes -> 64 contiguous bytes)
   float* slab = a.slabs + (size_t)blockIdx.x * TAPS * a.cout_p * a.cin_p;
 #pragma unroll
@@ -566,7 +587,7 @@ __global__ __launch_bounds__(256, (KS == 3 && NCI * MTC >= 16) ? 1 : 2) void con
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int co = co0 + m * 16 + q * 4 + r, ci = ci0 + cit * 16 + p;
-          slab[((size_t)tap * a.cout_p + co) * a.cin_p + ci] = acc[m][c][r];
+          slab[((size_t)tap * a.cout_p + co) * a.cin_p + ci] = acc[NOX ? 0 : m][NOX ? 0 : c][r];
         }
     }
   }
@@ -681,7 +702,10 @@ static int launch_wgrad(const WgArgs& a, int gx, int gy, hipStream_t s) {
   if (a.wt) {  // the fused input gradient: 1x1 BatchNorm forms whose one Cout chunk is the whole layer (dy_conv1x1_wgrad_dgrad_supported)
     if constexpr (KS == 1) {
       if (!a.raw || gy != a.nci_chunks) return DY_ERR_ARG;
-      if (a.xs.nseg > 0) hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 7>), dim3(gx, gy), dim3(256), 0, s, a);
+      if (!a.x) {  // frozen layer (dy_conv1x1_dgrad_bn): the input gradient alone, no X operand
+        if (a.dxs.nseg > 0) hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 15>), dim3(gx, gy), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 13>), dim3(gx, gy), dim3(256), 0, s, a);
+      } else if (a.xs.nseg > 0) hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 7>), dim3(gx, gy), dim3(256), 0, s, a);
       else hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 5>), dim3(gx, gy), dim3(256), 0, s, a);
     } else return DY_ERR_ARG;
   } else if (a.raw && a.xs.nseg > 0) {
@@ -785,6 +809,7 @@ struct WgBnHost {  // BatchNorm + SiLU backward folded into the staging of dY (d
   unsigned dy_plane = 0;
   // dy_conv1x1_wgrad_dgrad_*: the input gradient from the same launch (WgArgs)
   const void* wt = nullptr; void* dx = nullptr; int lddx = 0, dx_acc = 0; const DySegs* dxs = nullptr;
+  bool dgrad_only = false;     // dy_conv1x1_dgrad_bn: x, slabs and dw are absent
 };
 static int conv_wgrad_impl(const void* x, int ldx, const void* dy, int lddy, float* slabs, float* dw, int n, int h, int w,
                            int cin, int cout, int ks, int stride, int accumulate, int ld_taps, int ld_cphys, int ld_cin,
@@ -919,6 +944,53 @@ static bool segs_in_valid(const DySegs* xs, int cin, int h, int w) {
         ((xs->acc[k] & 2) && ((h | w) & 1))) return false;
   return true;
 }
+// ---- the same for a layer whose parameters are frozen (conv_wgrad_kernel, BNF 13 / 15): d(raw) is formed while dY is staged and
+// multiplied by the transposed pack into dX; X is never read, nothing of the weight gradient exists.  One resident round of
+// workgroups: three per CU (the kernel's launch bounds) over the Cin-chunk rows of the grid.
+static int dgrad_only_columns(int ntiles, int gy) {
+  int gx = (256 * 3) / (gy > 0 ? gy : 1);
+  if (gx < 32) gx = 32;
+  if (gx > ntiles) gx = ntiles;
+  return gx < 1 ? 1 : gx;
+}
+extern "C" int dy_conv1x1_dgrad_bn_supported(int n, int h, int w, int cin, int cout) { return wgrad_dgrad_plan(n, h, w, cin, cout).ok; }
+extern "C" int dy_dgrad_only_kernel_name(int n, int h, int w, int cin, int cout, int segs, char* out, int cap) {
+  const WgDgPlan pl = wgrad_dgrad_plan(n, h, w, cin, cout);
+  if (!out || cap < 8 || !pl.ok) return DY_ERR_ARG;
+  snprintf(out, cap, "conv_wgrad_kernel<1, 1, %d, %d, %d>", pl.nci, pl.mtc, segs ? 15 : 13);
+  return DY_OK;
+}
+// One entry for the three operand conventions of dy_conv1x1_wgrad_dgrad_bn / _segs / _planes: dy2 != NULL = dY in two planes split at
+// csplit; dxs != NULL = dX per member of a concatenation (then dx is unused), else (dx, lddx, dx_accumulate).
+extern "C" int dy_conv1x1_dgrad_bn(const void* dy, const void* dy2, int lddy, int csplit, const void* raw, int ldraw, const float* coef,
+                                   const double* acc, float count, const void* w_packed_t, void* dx, int lddx, int dx_accumulate,
+                                   const DySegs* dxs, int n, int h, int w, int cin, int cout, hipStream_t stream) {
+  if (!dy || !raw || !coef || !acc || (ldraw & 7) || ((uintptr_t)raw & 15)) return DY_ERR_ARG;
+  if (!w_packed_t || ((uintptr_t)w_packed_t & 15) || !wgrad_dgrad_plan(n, h, w, cin, cout).ok) return DY_ERR_ARG;
+  long plane = 0;
+  if (dy2) {
+    if ((csplit & 7) || csplit <= 0 || csplit >= cout || ((uintptr_t)dy2 & 15)) return DY_ERR_ARG;
+    plane = (const char*)dy2 - (const char*)dy;
+    if (plane < (long)n * h * w * lddy * 2 || plane + (double)n * h * w * lddy * 2.0 >= 2147483648.0) return DY_ERR_ARG;
+  } else if (csplit) {
+    return DY_ERR_ARG;
+  }
+  if (dxs) {
+    if (dxs->nseg < 1 || dxs->nseg > DY_MAX_SEGS || dxs->c_end[dxs->nseg - 1] != cin) return DY_ERR_ARG;
+    for (int k = 0; k < dxs->nseg; ++k) {
+      const int cb = k ? dxs->c_end[k - 1] : 0;
+      if ((dxs->c_end[k] & 7) || dxs->c_end[k] <= cb || (dxs->ld[k] & 7) || dxs->ld[k] < dxs->c_end[k] - cb || !dxs->ptr[k] ||
+          ((uintptr_t)dxs->ptr[k] & 15) || (dxs->acc[k] & ~1)) return DY_ERR_ARG;
+    }
+  } else if (!dx || ((uintptr_t)dx & 15) || (lddx & 7) || lddx < cin || (double)n * h * w * lddx * 2.0 >= 2147483648.0) {
+    return DY_ERR_ARG;
+  }
+  WgBnHost bn{raw, nullptr, coef, acc, nullptr, nullptr, ldraw, count};
+  bn.dy_csplit = dy2 ? csplit : 0; bn.dy_plane = (unsigned)plane;
+  bn.wt = w_packed_t; bn.dxs = dxs; bn.dx = dxs ? nullptr : dx; bn.lddx = lddx; bn.dx_acc = dx_accumulate != 0;
+  bn.dgrad_only = true;
+  return conv_wgrad_impl(nullptr, 8, dy, lddy, nullptr, nullptr, n, h, w, cin, cout, 1, 1, 0, 0, 0, 0, stream, &bn);
+}
 // dy_conv_wgrad_bn (ks 1) that also leaves dX = W^T d(raw) in (dx, lddx), stored or (dx_accumulate) added: no draw, no second launch
 extern "C" int dy_conv1x1_wgrad_dgrad_bn(const void* x, int ldx, const void* dy, int lddy, const void* raw, int ldraw, const float* coef,
                                          const double* acc, float* dgamma, float* dbeta, float count, float* slabs, float* dw,
@@ -980,6 +1052,8 @@ static int conv_wgrad_impl(const void* x, int ldx, const void* dy, int lddy, flo
                            hipStream_t stream, const WgBnHost* bn) {
   if (!(ks == 1 || ks == 3) || !(stride == 1 || stride == 2) || (ks == 1 && stride != 1)) return DY_ERR_ARG;
   if ((ldx & 7) || (lddy & 7) || ((uintptr_t)x & 15) || ((uintptr_t)dy & 15)) return DY_ERR_ALIGN;
+  const bool dgrad_only = bn && bn->dgrad_only;
+  if (dgrad_only != (x == nullptr) || (dgrad_only && (!bn->wt || slabs || dw))) return DY_ERR_ARG;
   // staging uses 32-bit buffer offsets: one image (3x3) or the whole tensor (1x1) must stay below 2 GiB
   if ((ks == 1 ? (double)n : 1.0) * h * w * (ldx > lddy ? ldx : lddy) * 2.0 >= 2147483648.0) return DY_ERR_ARG;
   int cp, op, nci, mtc;
@@ -1023,6 +1097,7 @@ static int conv_wgrad_impl(const void* x, int ldx, const void* dy, int lddy, flo
   long slab_elems;
   dy_wgrad_workspace(n, h, w, cin, cout, ks, stride, &nslabs, &slab_elems);
   const int gy = a.nci_chunks * nco_chunks;
+  if (dgrad_only) nslabs = dgrad_only_columns(a.ntiles, gy);  // no slab per workgroup: the grid is sized by residency alone
   int rc;
   if (ks == 1) rc = dispatch_wgrad<1, 1>(nci, mtc, a, nslabs, gy, stream);
   else if (stride == 1) rc = dispatch_wgrad<3, 1>(nci, mtc, a, nslabs, gy, stream);

@@ -21,6 +21,15 @@ from ..utils import LOGGER, RANK
 from ..utils.torch_utils import ModelEMA, init_seeds, select_device
 
 
+def frozen_parameter_names(names, freeze):
+    """The reference's freeze rule (engine/trainer.py:662-682) as a pure function: ``freeze`` is an int n (layers ``range(n)``), a list of
+    layer indices or None; a parameter is frozen when ``f"model.{i}."`` of one of those layers, or ``".dfl"`` (always), is a substring of
+    its name.  Returns the frozen names in the order given; every other parameter is trainable."""
+    layers = freeze if isinstance(freeze, list) else range(freeze) if isinstance(freeze, int) else []
+    keys = [f"model.{x}." for x in layers] + [".dfl"]
+    return [k for k in names if any(x in k for x in keys)]
+
+
 class DetectionTrainer:
     def __init__(self, model=None, cfg=None, overrides=None, _callbacks=None):
         """``DetectionTrainer(model, overrides=...)`` (this package's YOLO facade) or, as in the reference
@@ -75,8 +84,18 @@ class DetectionTrainer:
             broadcast_buffers(rt.flat_p, 0)
             broadcast_buffers(rt.flat_b, 0)
             rt.mark_dirty()
-        for k, v in self.model.named_parameters():  # always freeze .dfl (engine/trainer.py:670)
-            v.requires_grad = ".dfl" not in k
+        # Freeze layers (reference engine/trainer.py:662-682).  BatchNorm of a frozen layer stays in training mode, as there: its forward
+        # uses batch statistics and its running statistics keep moving; the step plan built below traces under these flags and leaves
+        # the frozen layers' backward work out (hip/engine.py).
+        frozen = frozen_parameter_names([k for k, _ in self.model.named_parameters()], a.freeze)
+        for k, v in self.model.named_parameters():
+            if k in frozen:
+                LOGGER.info(f"Freezing layer '{k}'")
+                v.requires_grad = False
+            elif not v.requires_grad:
+                LOGGER.info(f"WARNING ⚠️ setting 'requires_grad=True' for frozen layer '{k}'. "
+                            "See ultralytics.engine.trainer for customization of frozen layers.")
+                v.requires_grad = True
         global_bs = batch_size * self.world_size
         self.accumulate = max(round(a.nbs / global_bs), 1)
         self.wd = a.weight_decay * global_bs * self.accumulate / a.nbs
@@ -216,6 +235,11 @@ class DetectionTrainer:
                 cap = max(16, 2 * v8DetectionLoss.capacity_for(first, batch_size))
                 del first
             a.nmax = cap
+        if a.resume and a.freeze is None:  # a resumed run keeps what the checkpoint's run froze (reference check_resume: its train_args)
+            path = a.resume if isinstance(a.resume, str) else a.model
+            if path and str(path).endswith(".pt") and os.path.exists(str(path)):
+                ck = torch.load(path, map_location="cpu", weights_only=False)
+                a.freeze = (ck.get("train_args") or {}).get("freeze") if isinstance(ck, dict) else None
         self.setup(nb, batch_size, imgsz)
         self.start_epoch = self.resume_training(a.resume) if a.resume else 0
         self.save_dir = self._save_dir()

@@ -143,6 +143,9 @@ SIGNATURES = {
                                              i32, i32, i32, i32, vp]),
     "dy_conv1x1_wgrad_dgrad_bn_planes": (i32, [C.POINTER(DySegs), vp, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, f32, vp, vp, vp, vp, i32, i32,
                                                C.POINTER(DySegs), i32, i32, i32, i32, i32, i32, vp]),
+    "dy_conv1x1_dgrad_bn_supported": (i32, [i32, i32, i32, i32, i32]),
+    "dy_dgrad_only_kernel_name": (i32, [i32, i32, i32, i32, i32, i32, C.c_char_p, i32]),
+    "dy_conv1x1_dgrad_bn": (i32, [vp, vp, i32, i32, vp, i32, vp, vp, f32, vp, vp, i32, i32, C.POINTER(DySegs), i32, i32, i32, i32, i32, vp]),
     "dy_bn_act_apply_acc_group": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dy_bn_act_bwd_reduce_acc_group": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dy_bn_act_bwd_reduce_rows": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, vp, i32, i32, vp]),

@@ -117,6 +117,10 @@ BN_DGRED = BN_WGRAD and os.environ.get("DY_BN_DGRED", "0") != "0"
 # The input gradient of a 1x1 Conv formed by its weight-gradient kernel from the d(raw) tile it holds in LDS (csrc/conv_wgrad.hip, BNF 5 / 7):
 # no d(raw) round trip through HBM and no input-gradient launch where dy_conv1x1_wgrad_dgrad_supported says so.  0 = the two-launch list.
 WGRAD_DGRAD = BN_WGRAD and not BN_DGRED and os.environ.get("DY_WGRAD_DGRAD", "1") != "0"
+# A FROZEN 1x1 Conv + BatchNorm + SiLU (requires_grad False on its weight, gamma and beta: trainer freeze=...) whose input needs a gradient:
+# d(raw) formed and multiplied into dX by ONE launch that reads no X and writes nothing of the weight gradient (csrc/conv_wgrad.hip, BNF 13 /
+# 15, dy_conv1x1_dgrad_bn) where dy_conv1x1_dgrad_bn_supported says so.  0 = the two-launch form: dy_bn_act_bwd_apply_acc, then the input gradient.
+FROZEN_DGRAD = BN_WGRAD and not BN_DGRED and os.environ.get("DY_FROZEN_DGRAD", "1") != "0"
 BN_DGRED_MAXC = int(os.environ.get("DY_BN_DGRED_MAXC", "64"))
 BN_DGRED_MAXPIX = int(os.environ.get("DY_BN_DGRED_MAXPIX", str(1 << 40)))  # ... and the map size (N*H*W): small maps are latency-bound
 
@@ -170,6 +174,17 @@ class Storage:
         self.gbuf = None
         self.gwritten = []  # list of (c0, c1) already holding gradient
 
+    nograd = ()  # channel ranges (c0, c1) whose producer found that no gradient will ever be asked of them (Engine._no_grad)
+
+    def grad_free(self, c0, c1):
+        """Every channel of [c0, c1) lies in a range a producer marked as needing no gradient."""
+        pos = c0
+        for a, b in sorted(self.nograd):
+            if a > pos:
+                break
+            pos = max(pos, b)
+        return pos >= c1
+
     def act(self, c0=0, C=None):
         return Act(self, c0, self.C - c0 if C is None else C)
 
@@ -195,8 +210,10 @@ class Act:
     """Channel slice of a Storage; the unit every op consumes/produces."""
     __slots__ = ("st", "c0", "C", "needs_grad")
 
-    def __init__(self, st, c0, C, needs_grad=True):
+    def __init__(self, st, c0, C, needs_grad=None):
         assert c0 % 8 == 0 and C % 8 == 0 and c0 + C <= st.C
+        if needs_grad is None:  # a new view of channels whose producer pruned its backward needs no gradient either
+            needs_grad = not (st.nograd and st.grad_free(c0, c0 + C))
         self.st, self.c0, self.C, self.needs_grad = st, c0, C, needs_grad
 
     N = property(lambda s: s.st.N)
@@ -376,6 +393,8 @@ class ConvSpec:
         self.acc_bias = None            # convs with bias: [DY_BN_COPIES][round8(cout)] sums of dY (bias gradient)
         self.gweight = self.gbias = self.gbn_w = self.gbn_b = None  # fp32 gradient views
 
+    trainable = True  # False: every parameter of the layer is frozen (Runtime._bind_grads); its gradient views are sinks
+
 
 class Engine:
     """Owns scratch memory, the tape, the recorder and the stream handle; all ops are methods."""
@@ -529,6 +548,28 @@ class Engine:
             elif isinstance(x, Act) and x.needs_grad:
                 d = self._uses.setdefault(id(x.st), {})
                 d[(x.c0, x.C)] = d.get((x.c0, x.C), 0) + 1
+
+    # ---- pruned backward: an op's output needs a gradient iff one of its inputs does or the op owns a trainable parameter; an op whose
+    # output needs none leaves nothing on the tape and marks what it wrote, so that every later view of those channels knows
+    def _live(self, spec, *xs):
+        return self.tape is None or (spec is not None and spec.trainable) or any(x is not None and x.needs_grad for x in xs)
+
+    def _no_grad(self, *ys):
+        for y in ys:
+            if isinstance(y, SegAct):
+                self._no_grad(*y.parts)
+            elif isinstance(y, Act):
+                y.needs_grad = False
+                y.st.nograd = list(y.st.nograd) + [(y.c0, y.c0 + y.C)]
+
+    def _record(self, live, ys, f):
+        """The backward closure of the op being traced, or -- its output needs no gradient -- the mark on its outputs instead."""
+        if self.tape is None:
+            return
+        if live:
+            self.tape.append(f)
+        else:
+            self._no_grad(*(ys if isinstance(ys, (list, tuple)) else [ys]))
 
     def _sole_consumer_of_conv(self, x):
         """(spec, raw) of the Conv whose output IS ``x`` when the op now writing x's gradient is the only one that ever will: every
@@ -720,9 +761,23 @@ class Engine:
         t = DySegs()
         assert len(x.parts) <= 8
         t.nseg, end = len(x.parts), 0
+        # ``grad``: a member that needs no gradient still receives its pieces of W^T d(raw) from a kernel that writes the whole
+        # concatenation -- they go to a sink (stored, never read); the member's own storage gets no gradient twin and is never written
+        sink, offs = None, {}
+        if grad:
+            need = 0
+            for i, q in enumerate(x.parts):
+                if not q.needs_grad:
+                    offs[i] = need
+                    need += (q.npix * q.C * 2 + 255) // 256 * 256
+            if offs:
+                sink = self.scratch("dx_sink", need)
         for i, q in enumerate(x.parts):
             end += q.C
             up = isinstance(q, UpAct)
+            if i in offs:
+                t.c_end[i], t.ld[i], t.ptr[i], t.acc[i] = end, q.C, sink.data_ptr() + offs[i], 0
+                continue
             t.c_end[i], t.ld[i], t.ptr[i] = end, (q.gld if (grad and up) else q.ld), (q.gptr if grad else q.ptr)
             t.acc[i] = int(acc[i]) if acc is not None else (2 if (up and not grad) else 0)
         return t
@@ -818,7 +873,9 @@ class Engine:
         Ho, Wo = self.out_hw(spec, x)
         raw = self.new_act(x.N, Ho, Wo, spec.cout)
         y = out if out is not None else self.new_act(x.N, Ho, Wo, spec.cout)
-        self._use(x, res)
+        live = self._live(spec, x, res)
+        if live:
+            self._use(x, res)
         planes = isinstance(y, SegAct)  # the output as two planes (new_planes; the caller asked planes_ok)
         if self.tape is not None and not planes:
             self._prod[(id(y.st), y.c0, y.C)] = (spec, raw)
@@ -833,8 +890,7 @@ class Engine:
             self.call("dy_bn_act_apply_acc_split", raw.ptr, raw.ld, y0.ptr, y0.ld, y1.ptr, y1.ld, y0.C, spec.acc_f.data_ptr(),
                       bn["weight"].data_ptr(), bn["bias"].data_ptr(), bn["running_mean"].data_ptr(), bn["running_var"].data_ptr(),
                       spec.coef.data_ptr(), npix, spec.cout, spec.act, float(npix), spec.bn_eps, spec.bn_mom)
-            if self.tape is not None:
-                self.tape.append(lambda: self._conv_bn_act_bwd(spec, x, raw, y, None))
+            self._record(live, y, lambda: self._conv_bn_act_bwd(spec, x, raw, y, None))
             return y
         if acc:
             # statistics through the fp64 accumulator: conv adds, the apply kernel below finishes them in its prologue
@@ -862,8 +918,7 @@ class Engine:
         if not acc:
             self.call("dy_bn_act_apply", raw.ptr, raw.ld, 0 if res is None else res.ptr, 0 if res is None else res.ld, y.ptr, y.ld,
                       spec.coef.data_ptr(), npix, spec.cout, spec.act)
-        if self.tape is not None:
-            self.tape.append(lambda: self._conv_bn_act_bwd(spec, x, raw, y, res))
+        self._record(live, y, lambda: self._conv_bn_act_bwd(spec, x, raw, y, res))
         return y
 
     @staticmethod
@@ -882,7 +937,9 @@ class Engine:
         self.call("dy_bn_act_apply_acc", raw.ptr, raw.ld, 0, 0, y.ptr, y.ld, spec.acc_f.data_ptr(), bn["weight"].data_ptr(),
                   bn["bias"].data_ptr(), bn["running_mean"].data_ptr(), bn["running_var"].data_ptr(), spec.coef.data_ptr(), npix, spec.cout,
                   spec.act, float(npix), spec.bn_eps, spec.bn_mom)
-        if self.tape is not None:
+        if self.tape is not None and not spec.trainable:  # a frozen stem has no backward at all: no input gradient exists either
+            self._no_grad(y)
+        elif self.tape is not None:
             def bwd():
                 assert y.grad_ready(), f"gradient of {spec.name} output incomplete"
                 self.call("dy_bn_act_bwd_reduce_acc", y.gptr, y.ld, raw.ptr, raw.ld, spec.coef.data_ptr(), self._acc_ready(spec.acc_b), npix,
@@ -911,7 +968,7 @@ class Engine:
         defer = list(defer) if defer is not None else [False] * len(members)
         ok = (BN_GROUP and self.training and self.tape is not None and 1 < len(members) <= self.L.dy_bn_group_max()
               and all(sp.acc_f is not None and sp.acc_b is not None and sp.act == DY_ACT_SILU and sp.ld is None and not isinstance(x, ImageAct)
-                      for sp, x in members))
+                      and self._live(sp, x) for sp, x in members))
         if not ok:
             return [self.conv_bn_act(sp, x, defer_apply=d) for (sp, x), d in zip(members, defer)]
         outs = []
@@ -972,6 +1029,10 @@ class Engine:
             npix = y0.npix
             self.call("dy_bn_act_bwd_reduce_acc_split", y0.gptr, y0.ld, y1.gptr, y1.ld, y0.C, raw.ptr, raw.ld, spec.coef.data_ptr(),
                       self._acc_ready(spec.acc_b), npix, spec.cout, spec.act)
+            if not spec.trainable and self._dgrad_only_ok(spec, x):  # frozen: the input gradient alone, from the two planes of dY
+                self._dgrad_only(spec, x, raw, y0.gptr, y0.ld, npix, planes=(y1.gptr, y0.C))
+                return
+            # (a frozen layer in planes without that kernel keeps the trainable launches: its parameter gradients land in the sinks)
             if self._wgrad_dgrad_ok(spec, x):
                 draw = None  # the fused launch keeps d(raw) in LDS
             elif self.cur_sid:
@@ -1018,9 +1079,19 @@ class Engine:
                       spec.cout, spec.act, C.byref(n))
             self.call("dy_bn_bwd_finalize", part.data_ptr(), n.value, spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(),
                       spec.bwdcoef.data_ptr(), spec.cout, float(npix), 0)
-        side_small = bool(SIDE_SMALL and npix <= SIDE_SMALL and self.deferred_wgrad is not None and not self.cur_sid and not self.side_wgrad
+        frozen = not spec.trainable
+        if frozen:
+            # The BatchNorm backward sums above are still needed (batch statistics are live in a frozen layer, as in the reference); what
+            # follows is d(raw) and the input gradient only: no weight-gradient launch, no slabs, no reduce descriptor, and the
+            # gamma / beta sums of the two-launch form go to the sinks.
+            if not x.needs_grad:
+                return  # (only the shortcut carried a gradient on)
+            if acc and spec.act == DY_ACT_SILU and self._dgrad_only_ok(spec, x):
+                self._dgrad_only(spec, x, raw, y.gptr, y.ld, npix)
+                return
+        side_small = bool(not frozen and SIDE_SMALL and npix <= SIDE_SMALL and self.deferred_wgrad is not None and not self.cur_sid and not self.side_wgrad
                           and acc and isinstance(x, Act) and x.needs_grad and spec.ld is None)
-        bn_wgrad = bool(acc and BN_WGRAD and spec.act == DY_ACT_SILU and not self.side_wgrad and not side_small and raw.ld == spec.cout)
+        bn_wgrad = bool(not frozen and acc and BN_WGRAD and spec.act == DY_ACT_SILU and not self.side_wgrad and not side_small and raw.ld == spec.cout)
         if bn_wgrad and self._wgrad_dgrad_ok(spec, x):
             draw = None  # the fused launch keeps d(raw) in LDS
         elif ((self.side_wgrad or side_small) and self.deferred_wgrad is not None) or self.cur_sid:
@@ -1030,7 +1101,7 @@ class Engine:
             self.hold(draw)
         else:
             draw = self.scratch("draw", npix * spec.cout * 2)
-        if acc and BN_WGRAD and spec.act == DY_ACT_SILU and not self.side_wgrad and not side_small and raw.ld == spec.cout:
+        if bn_wgrad:
             # no apply launch: the weight-gradient kernel forms d(raw) while staging and leaves it in ``draw`` for the dgrad
             bn = (raw, draw, spec.coef.data_ptr(), spec.acc_b.data_ptr(), spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(), float(npix))
             self._conv_bwd(spec, x, y.gptr, y.ld, y.H, y.W, bn=bn)
@@ -1041,7 +1112,27 @@ class Engine:
         else:
             self.call("dy_bn_act_bwd_apply", y.gptr, y.ld, raw.ptr, raw.ld, draw.data_ptr(), spec.cout, spec.coef.data_ptr(),
                       spec.bwdcoef.data_ptr(), npix, spec.cout, spec.act, 0)
-        self._conv_bwd(spec, x, draw.data_ptr(), spec.cout, y.H, y.W, side_hint=side_small)
+        self._conv_bwd(spec, x, draw.data_ptr(), spec.cout, y.H, y.W, side_hint=side_small, wgrad=not frozen)
+
+    def _dgrad_only_ok(self, spec, x):
+        """The backward of the FROZEN ``spec`` (1x1 Conv + BatchNorm + SiLU, accumulator statistics) over ``x`` is ONE launch that forms
+        d(raw) and the input gradient and nothing else (dy_conv1x1_dgrad_bn).  It keeps d(raw) in LDS and uses no shared scratch, so
+        branch and side-stream backward passes may take it too."""
+        if not (FROZEN_DGRAD and BN_ACC and spec.bn is not None and spec.acc_b is not None and spec.act == DY_ACT_SILU and spec.ks == 1
+                and spec.stride == 1 and spec.ld is None and isinstance(x, (Act, SegAct)) and x.needs_grad
+                and spec.cout == spec.cout_phys and spec.cin == spec.cin_phys):
+            return False
+        return bool(self.L.dy_conv1x1_dgrad_bn_supported(x.N, x.H, x.W, spec.cin, spec.cout))
+
+    def _dgrad_only(self, spec, x, raw, dy_ptr, lddy, npix, planes=None):
+        if isinstance(x, SegAct):
+            accs = [q.grad_target() if q.needs_grad else 0 for q in x.parts]
+            dxs, dx = C.byref(self._segs(x, grad=True, acc=accs)), (0, 0, 0)
+        else:
+            acc = x.grad_target()
+            dxs, dx = None, (x.gptr, x.ld, int(acc))
+        self.call("dy_conv1x1_dgrad_bn", dy_ptr, planes[0] if planes else 0, lddy, planes[1] if planes else 0, raw.ptr, raw.ld,
+                  spec.coef.data_ptr(), spec.acc_b.data_ptr(), float(npix), spec.wpack_t.data_ptr(), *dx, dxs, x.N, x.H, x.W, spec.cin, spec.cout)
 
     def _wgrad_dgrad_ok(self, spec, x):
         """The backward of ``spec`` (a 1x1 Conv + BatchNorm + SiLU on the BatchNorm-in-the-weight-gradient path) over input ``x`` is ONE
@@ -1050,18 +1141,23 @@ class Engine:
         if not (WGRAD_DGRAD and spec.ks == 1 and spec.stride == 1 and spec.ld is None and isinstance(x, (Act, SegAct)) and x.needs_grad
                 and not self.cur_sid and not self.side_wgrad and spec.cout == spec.cout_phys and spec.cin == spec.cin_phys):
             return False
-        if isinstance(x, SegAct) and not all(q.needs_grad for q in x.parts):
-            return False
+        # (a concatenation with members that need no gradient -- their producers are frozen -- takes it too: their pieces go to a sink, _segs)
         return bool(self.L.dy_conv1x1_wgrad_dgrad_supported(x.N, x.H, x.W, spec.cin, spec.cout))
 
-    def _conv_bwd(self, spec, x, dy_ptr, lddy, Ho, Wo, accumulate_w=0, defer=True, bn=None, bias_acc=None, planes=None, side_hint=False):
+    def _conv_bwd(self, spec, x, dy_ptr, lddy, Ho, Wo, accumulate_w=0, defer=True, bn=None, bias_acc=None, planes=None, side_hint=False,
+                  wgrad=True):
         """weight gradient + input gradient of one convolution given d(raw output) (fp16, (N,Ho,Wo,lddy)).
         When the engine is collecting (``self.deferred_wgrad`` is a list: StepPlan's backward trace) the per-workgroup slabs of
         this layer are kept and reduced together with every other layer's by ONE ``dy_wgrad_reduce_batched`` launch at the end
         of the backward pass; weights shared by several calls (ScalSeq's conv3d: ``defer=False``) reduce immediately."""
+        if not wgrad:  # a frozen layer (dy_ptr = d(raw) from the apply launch): the input gradient is all there is
+            assert bn is None and bias_acc is None and planes is None
+            return self._input_grad(spec, x, dy_ptr, lddy, Ho, Wo)
         ns, se = C.c_int(), C.c_long()
         self.L.dy_wgrad_workspace(x.N, x.H, x.W, spec.cin, spec.cout, spec.ks, spec.stride, C.byref(ns), C.byref(se))
         deferred = defer and not accumulate_w and self.deferred_wgrad is not None
+        if self.wgrad_log is not None and not deferred:
+            self.wgrad_log.append(spec)
         if deferred:
             slabs = self.transient((ns.value * se.value,), torch.float32)
             self.hold(slabs)
@@ -1081,7 +1177,7 @@ class Engine:
             assert not side and self._wgrad_dgrad_ok(spec, x)
             seg = isinstance(x, SegAct)
             if seg:
-                accs = [q.grad_target() for q in x.parts]
+                accs = [q.grad_target() if q.needs_grad else 0 for q in x.parts]
                 dxs, dx = C.byref(self._segs(x, grad=True, acc=accs)), (0, 0, 0)
             else:
                 acc = x.grad_target()
@@ -1133,10 +1229,16 @@ class Engine:
                       spec.cin, spec.cout, spec.ks, spec.stride, accumulate_w, side=side)
         if isinstance(x, SegAct):
             assert bn is not None, f"{spec.name}: a segmented input needs the BatchNorm-in-the-weight-gradient path"
+        self._input_grad(spec, x, dy_ptr, lddy, Ho, Wo)
+
+    wgrad_log = None  # a list while a StepPlan traces its backward: the ConvSpec behind every reduce descriptor and every weight-gradient
+                      # launch that reduces at once
+
+    def _input_grad(self, spec, x, dy_ptr, lddy, Ho, Wo):
+        """dX = W^T d(raw) of one convolution, d(raw) fp16 at (dy_ptr, lddy): into x's gradient, stored or added (first writer stores)."""
+        if isinstance(x, SegAct):
             if x.needs_grad:  # every 8-channel piece of W^T d(raw) goes to its member's gradient tensor, stored or added per member
-                accs = [q.grad_target() if q.needs_grad else 0 for q in x.parts]
-                if not all(q.needs_grad for q in x.parts):  # a member without a gradient still receives its pieces: give it a sink
-                    raise NotImplementedError("a concatenation member that needs no gradient beside members that do")
+                accs = [q.grad_target() if q.needs_grad else 0 for q in x.parts]  # (a member that needs none gets a sink: _segs)
                 self.call("dy_conv1x1_input_grad_segs", dy_ptr, lddy, spec.wpack_t.data_ptr(), C.byref(self._segs(x, grad=True, acc=accs)),
                           x.N, Ho, Wo, spec.cout_phys, spec.cin)
             return
@@ -1169,6 +1271,8 @@ class Engine:
             self._side_used = False
         if not items:
             return
+        if self.wgrad_log is not None:
+            self.wgrad_log.extend(it[0] for it in items)
         sz = self.L.dy_wgrad_reduce_desc_bytes()
         host = (C.c_char * (sz * len(items)))()
         blocks = 0
@@ -1217,9 +1321,11 @@ class Engine:
         (ptr, ld) of the fp16 gradient w.r.t. the output at backward time.  ``rows_level``: this is the box branch of detection
         level ``rows_level`` -- its output gradient is non-zero at foreground anchors only (see HEAD_ROWS)."""
         x = self.dense(x)
-        self._use(x)
+        live = self._live(spec, x)  # (a frozen conv whose input needs no gradient either: nothing to back-propagate)
+        if live:
+            self._use(x)
         self._conv_raw(spec, x, y_ptr, ldy, DY_EPI_BIAS | (DY_EPI_F32OUT if f32out else 0), 0, spec.bias)
-        if self.tape is not None:
+        if self.tape is not None and live:
             if (rows_level is not None and self.rows_used is not None and spec.ks == 1 and spec.ld is None and spec.acc_bias is not None
                     and self.L.dy_conv1x1_rows_supported(spec.cin, spec.cout)):
                 self.rows_used.add(rows_level)
@@ -1414,13 +1520,13 @@ class Engine:
         y = out if out is not None else self.new_act(x.N, 2 * x.H, 2 * x.W, x.C)
         self._use(x)
         self.call("dy_upsample2x", x.ptr, x.ld, y.ptr, y.ld, x.N, x.H, x.W, x.C, 0, 0)
-        if self.tape is not None:
-            def bwd():
-                if optional and not y.st.gwritten:
-                    return
-                acc = x.grad_target()
-                self.call("dy_upsample2x", y.gptr, y.ld, x.gptr, x.ld, x.N, x.H, x.W, x.C, 1, acc)
-            self.tape.append(bwd)
+
+        def bwd():
+            if optional and not y.st.gwritten:
+                return
+            acc = x.grad_target()
+            self.call("dy_upsample2x", y.gptr, y.ld, x.gptr, x.ld, x.N, x.H, x.W, x.C, 1, acc)
+        self._record(self._live(None, x), y, bwd)
         return y
 
     def maxpool5(self, x: Act, out: Act):
@@ -1429,11 +1535,11 @@ class Engine:
         self.hold(arg)
         self._use(x)
         self.call("dy_maxpool5", x.ptr, x.ld, out.ptr, out.ld, arg.data_ptr(), x.N, x.H, x.W, x.C)
-        if self.tape is not None:
-            def bwd():
-                acc = x.grad_target()
-                self.call("dy_maxpool5_backward", out.gptr, out.ld, arg.data_ptr(), x.gptr, x.ld, x.N, x.H, x.W, x.C, acc)
-            self.tape.append(bwd)
+
+        def bwd():
+            acc = x.grad_target()
+            self.call("dy_maxpool5_backward", out.gptr, out.ld, arg.data_ptr(), x.gptr, x.ld, x.N, x.H, x.W, x.C, acc)
+        self._record(self._live(None, x), out, bwd)
         return out
 
     def sppf_pools(self, cat, c_):
@@ -1445,7 +1551,9 @@ class Engine:
                 self.maxpool5(cat.act(j * c_, c_), cat.act((j + 1) * c_, c_))
             return
         sl = [cat.act(j * c_, c_) for j in range(4)]
-        taping = self.tape is not None
+        taping = self.tape is not None and sl[0].needs_grad
+        if self.tape is not None and not taping:  # cv1 is frozen and its input needs no gradient: neither do the pooled copies
+            self._no_grad(*sl[1:])
         args = [self.transient((x.npix * c_,), torch.uint8) for _ in range(3)] if taping else [None] * 3
         if taping:
             self.hold(*args)
@@ -1472,7 +1580,9 @@ class Engine:
         assert len(xs) <= 3
         self._use(*xs)
         self.call("dy_add", a.ptr, a.ld, b.ptr, b.ld, 0 if c is None else c.ptr, 0 if c is None else c.ld, y.ptr, y.ld, a.npix, a.C)
-        if self.tape is not None:
+        if self.tape is not None and not self._live(None, *xs):
+            self._no_grad(y)
+        elif self.tape is not None:
             def bwd():
                 shared = False
                 for t in xs:
@@ -1528,7 +1638,9 @@ class Engine:
                 self.call("dy_copy_slice", t.ptr, t.ld, y.ptr + 2 * off, y.ld, t.npix, t.C)
             parts.append((t, off))
             off += t.C
-        if self.tape is not None:
+        if self.tape is not None and not self._live(None, *xs):
+            self._no_grad(y)
+        elif self.tape is not None:
             def bwd():
                 for t, o in parts:
                     if not t.needs_grad:
@@ -1554,7 +1666,9 @@ class Engine:
         self.call("dy_zoom_pool", l.ptr, l.ld, yl.ptr, yl.ld, l.N, m.H, m.W, l.C)
         self.call("dy_copy_slice", m.ptr, m.ld, ym.ptr, ym.ld, m.npix, m.C)
         self.call("dy_upsample2x", s.ptr, s.ld, ys.ptr, ys.ld, s.N, s.H, s.W, s.C, 0, 0)
-        if self.tape is not None:
+        if self.tape is not None and not self._live(None, l, m, s):
+            self._no_grad(y)
+        elif self.tape is not None:
             def bwd():
                 if l.needs_grad:
                     acc = l.grad_target()
@@ -1604,12 +1718,16 @@ class Engine:
             self.call("dy_bn_eval_coef", bn3d["weight"].data_ptr(), bn3d["bias"].data_ptr(), bn3d["running_mean"].data_ptr(),
                       bn3d["running_var"].data_ptr(), coef.data_ptr(), Cc, BN3D_EPS)
         y = out if out is not None else self.new_act(N, H, W, Cc)
+        live = self._live(conv3d, *ps, res)
         if res is not None:
             assert (res.N, res.H, res.W, res.C) == (N, H, W, Cc)
-            self._use(res)
+            if live:
+                self._use(res)
         self.call("dy_scalseq_tail", raws[0].ptr, raws[0].ld, raws[1].ptr, raws[1].ld, raws[2].ptr, raws[2].ld,
                   0 if res is None else res.ptr, 0 if res is None else res.ld, y.ptr, y.ld, coef.data_ptr(), N, H, W, Cc)
-        if self.tape is not None:
+        if self.tape is not None and not live:
+            self._no_grad(y)
+        elif self.tape is not None:
             def bwd():
                 if res is not None and res.needs_grad:  # d(sum)/d(res) = identity, as in Engine.add
                     if (ADD_ALIAS and res.st.gbuf is None and not res.st.gwritten and res.c0 == 0 and res.C == res.st.C and y.c0 == 0
@@ -1655,11 +1773,15 @@ class Engine:
             doff = torch.zeros((x.N, h, w, 8 * ((2 * Np + 7) // 8)), dtype=torch.float16, device=self.device)
             self.hold(doff)
         self.conv_bias(sp_p, x, off.data_ptr(), 2 * Np, True, lambda: (doff.data_ptr(), doff.shape[-1]))
-        self._use(x)  # the sampler's backward writes x's gradient too
+        live = self._live(sp_p, x)  # the sampler's backward feeds p_conv's parameters (the offsets) and x
+        if live:
+            self._use(x)  # the sampler's backward writes x's gradient too
         xo = self.new_act(x.N, h, w, Np * x.C)
         self.call("dy_ldconv_sample", x.ptr, x.ld, off.data_ptr(), 2 * Np, pn_i32.data_ptr(), xo.ptr, xo.ld, x.N, x.H, x.W, h, w,
                   x.C, Np, stride)
-        if self.tape is not None:
+        if self.tape is not None and not live:
+            self._no_grad(xo)
+        elif self.tape is not None:
             def bwd():
                 assert xo.grad_ready()
                 if not x.needs_grad:  # stem: offset gradient only

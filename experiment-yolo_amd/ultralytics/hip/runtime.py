@@ -31,6 +31,7 @@ class Runtime:
             if isinstance(m, HipModule):
                 m._build_specs(self)
         self._pack_sig = None
+        self.refresh_frozen()  # parameters already frozen at construction: their gradients go to the sink from the start
 
     # ---- flat parameter / buffer storage -------------------------------------------------------------------------
     def _flatten(self):
@@ -115,14 +116,50 @@ class Runtime:
                 mod.__dict__["rt"] = self
 
     def refresh_frozen(self):
-        """Re-read ``requires_grad`` flags (BaseTrainer freezes '.dfl' after construction, engine/trainer.py:670-683)."""
+        """Re-read ``requires_grad`` flags (BaseTrainer freezes '.dfl' and the ``freeze=`` layers after construction, engine/trainer.py:
+        662-682).  The optimizer mask follows them, and so does WHERE every ConvSpec's parameter gradients go: a trainable parameter's
+        into its view of the flat gradient buffer, a frozen one's into a sink of its own that nothing reads -- the flat gradient of a
+        frozen parameter is exactly zero after every backward pass, so it enters neither the clip norm nor an all-reduce.  Launch lists
+        record these pointers: a StepPlan traced before a flag changed refuses to run afterwards (StepPlan._check_flags)."""
+        flags = tuple(p.requires_grad for _, p in self.root.named_parameters())
+        if flags == getattr(self, "_flags", None):
+            return
+        self._flags = flags
         self.frozen.zero_()
+        need, offs = 0, {}
         for n, p in self.root.named_parameters():
             o, k = self.param_off[n], p.numel()
             if not p.requires_grad:
                 self.frozen[o:o + _round(k)] = 1
+                offs[n] = need
+                need += _round(k)
             else:
                 self.frozen[o + k:o + _round(k)] = 1
+        self.flat_g.masked_fill_(self.frozen.bool(), 0.0)
+        if need > (self.flat_sink.numel() if self.flat_sink is not None else 0):
+            self.flat_sink = torch.zeros(need, dtype=torch.float32, device=self.eng.device)
+            self.eng.keep.append(self.flat_sink)  # (launch lists recorded under earlier flags may still name the old one)
+        for n, p in self.root.named_parameters():
+            o, k = self.param_off[n], p.numel()
+            src, o = (self.flat_g, o) if p.requires_grad else (self.flat_sink, offs[n])
+            self.gviews[id(p)] = src[o:o + k].view(p.shape)
+        for sp in self.specs.values():
+            self._bind_grads(sp)
+
+    flat_sink = None
+
+    def _bind_grads(self, sp):
+        """Point a ConvSpec's gradient views at where its parameters' gradients go now (``refresh_frozen``); ``sp.trainable``: it owns a
+        parameter that has one."""
+        prm = sp.params
+        g = {k: (None if v is None else self.gviews.get(id(v))) for k, v in prm.items()}
+        sp.gweight, sp.gbias = g["weight"], g["bias"]
+        if prm.get("bn_w") is not None:
+            sp.gbn_w, sp.gbn_b = g["bn_w"], g["bn_b"]
+        if prm.get("bn3d_w") is not None:
+            sp.gbn3d = (g["bn3d_w"], g["bn3d_b"])
+        # (a fused eval model's split convs hand in plain views, not Parameters: they have no gradient and are never trained)
+        sp.trainable = any(getattr(v, "requires_grad", False) for v in prm.values())
 
     # ---- conv specs -----------------------------------------------------------------------------------------------
     def _bn_dict(self, bn):
@@ -138,10 +175,8 @@ class Runtime:
         sp = ConvSpec(name, w2, None if conv.bias is None else conv.bias.data, None if bn is None else self._bn_dict(bn), ks,
                       stride, act, eps, mom)
         sp.ld = ld
-        sp.gweight = self.gviews.get(id(conv.weight))
-        sp.gbias = None if conv.bias is None else self.gviews.get(id(conv.bias))
-        if bn is not None:
-            sp.gbn_w, sp.gbn_b = self.gviews.get(id(bn.weight)), self.gviews.get(id(bn.bias))
+        sp.params = dict(weight=conv.weight, bias=conv.bias, bn_w=None if bn is None else bn.weight, bn_b=None if bn is None else bn.bias)
+        self._bind_grads(sp)
         self.eng.prepare_conv(sp)
         self.specs[key] = sp
         sp.packed = False

@@ -98,6 +98,20 @@ class StepPlan:
         self.dynamic_scale = bool(dynamic_scale)  # False (amp=False): the loss scale is a constant, nothing ever halves it
         self.opt_calls = 0                        # optimizer_step() calls so far; the device counts taken + skipped (state[5], state[6])
         self.rt.refresh_frozen()
+        self.flags = None        # {parameter name: requires_grad} the launch list was traced under (_trace_fb)
+        self.wgrad_specs = None  # the ConvSpec behind every weight-gradient reduction of the traced backward pass (tests, tools)
+
+    def _check_flags(self):
+        """A launch list is traced under the ``requires_grad`` flags it finds (trainer ``freeze=``): frozen layers' backward work is not
+        in it and their gradients have nowhere to go.  Running it under other flags would silently train (or not train) the wrong
+        parameters, so that raises, naming the first parameter that differs.  Host-side comparison, no device synchronisation."""
+        if self.flags is None:
+            return
+        for n, p in self.model.named_parameters():
+            if self.flags.get(n) != p.requires_grad:
+                raise RuntimeError(f"StepPlan: requires_grad of '{n}' is {p.requires_grad} now but was {self.flags.get(n)} when this step was "
+                                   "traced; a recorded launch list holds the backward of the parameters that were trainable then: build "
+                                   "a new StepPlan after changing what is frozen")
 
     # ---- host-side schedule ------------------------------------------------------------------------------------
     def set_hyper(self, lr, momentum, wd, ema_decay=None, max_norm=10.0, beta2=0.999, eps=1e-8):
@@ -115,6 +129,11 @@ class StepPlan:
     # ---- forward + loss + backward ----------------------------------------------------------------------------
     def _trace_fb(self, batch):
         eng, rt, model, crit = self.eng, self.rt, self.model, self.crit
+        rt.refresh_frozen()  # the flags as they are NOW decide what is traced and where parameter gradients go
+        self.flags = {n: p.requires_grad for n, p in model.named_parameters()}
+        if not any(self.flags.values()):
+            raise RuntimeError("StepPlan: every parameter of the model is frozen (requires_grad False): there is nothing to train")
+        eng.wgrad_log = []
         eng.rec = Recorder()
         eng.tape = []
         eng.training = True
@@ -182,12 +201,15 @@ class StepPlan:
                 for f in reversed(eng.tape[:mark]):
                     f()
             eng.flush_wgrad()
+            if self.fb_cut is not None and self.fb_cut >= len(eng.rec.ops):
+                self.fb_cut = None  # a frozen backbone left the second half without a launch: one bucket, exchanged at the optimizer step
         finally:
             eng.deferred_wgrad = None
             eng.rows_used = eng.loss_rows = eng.pending_decode = None
             eng.side_wgrad = False
             eng.acc_zeroed = False
             eng.arena = None
+            self.wgrad_specs, eng.wgrad_log = eng.wgrad_log, None
             rec, eng.rec, eng.tape = eng.rec, None, None
         self.ho = ho
         return rec
@@ -198,6 +220,7 @@ class StepPlan:
         under the backbone's backward, because it sums the gradient buffer IN PLACE (a micro-batch that is going to be accumulated must
         keep its local gradients: pass False)."""
         self._exchange = bool(exchange)
+        self._check_flags()
         if not self.input_act:
             self.stage(batch)
         n = self.crit.set_targets(batch, cap=self.B * self.nmax)
@@ -302,6 +325,7 @@ class StepPlan:
         """Forward + loss of the staged batch (the first half of the recorded list); returns the loss scalars.  The gradients w.r.t.
         the head outputs are written by the loss kernels at the plan's own loss scale (``state[0]``); nothing else of the backward
         pass runs."""
+        self._check_flags()
         self.stage(batch)
         n = self.crit.set_targets(batch, cap=self.B * self.nmax)
         if n > self.B * self.nmax:
@@ -775,6 +799,10 @@ class StepPlan:
             seg = name.endswith("segs") or (name.endswith("planes") and args[0] is not None)
             if L.dy_wgrad_dgrad_kernel_name(n, h, w, cin, cout, int(seg), buf, 128) == 0:
                 return buf.value.decode(), n * h * w * (2 * (cin + cout) + (0 if seg else old)) * 2
+        if name == "dy_conv1x1_dgrad_bn":  # a frozen 1x1 Conv: d(raw) and the input gradient in one launch, no X read (BNF 13 / 15)
+            n, h, w, cin, cout = args[14:19]
+            if L.dy_dgrad_only_kernel_name(n, h, w, cin, cout, int(args[13] is not None), buf, 128) == 0:
+                return buf.value.decode(), n * h * w * (cin + cout) * 2
         if name == "dy_conv_forward":
             n, h, w, cin, cout, ks, stride, dil = args[7:15]
             if dil == 2 and ks == 3:

@@ -41,7 +41,8 @@ class ScalSeq(HipModule):
                        running_var=self.bn.running_var)
         sp.coef3d = rt.eng.f32(4 * sp.cout)
         sp.bwdcoef3d = rt.eng.f32(2 * sp.cout)
-        sp.gbn3d = (rt.gviews[id(self.bn.weight)], rt.gviews[id(self.bn.bias)])
+        sp.params.update(bn3d_w=self.bn.weight, bn3d_b=self.bn.bias)
+        rt._bind_grads(sp)
 
     def forward_act(self, xs, out=None, res=None):
         p3, p4, p5 = xs

@@ -317,7 +317,8 @@ class BaseModel(HipModule):
         B, (H, W) = img.shape[0], (img.shape[1:3] if u8 else img.shape[2:4])
         nmax = self.criterion.capacity_for(batch, B)
         plans = self.__dict__.setdefault("_ag_plans", {})
-        key = (B, int(H), int(W), u8, dev)
+        # (a launch list holds the backward of the parameters that were trainable when it was traced: other flags, another list)
+        key = (B, int(H), int(W), u8, dev, tuple(p.requires_grad for p in self.parameters()))
         plan = plans.get(key)
         if plan is None or plan.nmax < nmax or plan.rt is not self.__dict__.get("rt"):
             # one recorded launch list per input geometry; fp16 backward at an internal loss scale that follows GradScaler's policy

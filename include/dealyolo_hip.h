@@ -188,6 +188,20 @@ int dy_conv1x1_wgrad_dgrad_bn_planes(const DySegs* xs, const void* x, int ldx, c
                                      float count, float* slabs, float* dw, const void* w_packed_t, void* dx, int lddx,
                                      int dx_accumulate, const DySegs* dxs, int n, int h, int w, int cin, int cout, int accumulate,
                                      hipStream_t stream);
+/* The input gradient ALONE of a 1x1 Conv + BatchNorm + SiLU whose weight, gamma and beta are frozen: reference nn/modules/conv.py:41-59
+ * under autograd with requires_grad=False parameters (engine/trainer.py:662-682, freeze=...), where BatchNorm stays in training mode, so
+ * the batch-statistics backward is still live but no parameter gradient exists.  d(raw) is formed from (dy, raw, coef, acc) while dY is
+ * staged and multiplied by w_packed_t into dX exactly as in dy_conv1x1_wgrad_dgrad_bn* -- same MFMA chains, same bits -- with NO X
+ * operand: nothing of the layer input is read, no slab, dgamma or dbeta is written.  One entry for the three operand conventions:
+ * dy2 != NULL = dY in two planes split at channel csplit (else csplit = 0); dxs != NULL = dX stored / added per member of a
+ * concatenation (c_end up to cin, acc 1 = add; dx unused), else (dx, lddx) stored or (dx_accumulate) added to.  Supported exactly where
+ * dy_conv1x1_wgrad_dgrad_supported is (dy_conv1x1_dgrad_bn_supported repeats it); dy_dgrad_only_kernel_name spells the instantiation
+ * (BNF 13, segs != 0: 15) as rocprofv3 prints it. */
+int dy_conv1x1_dgrad_bn_supported(int n, int h, int w, int cin, int cout);
+int dy_dgrad_only_kernel_name(int n, int h, int w, int cin, int cout, int segs, char* out, int cap);
+int dy_conv1x1_dgrad_bn(const void* dy, const void* dy2, int lddy, int csplit, const void* raw, int ldraw, const float* coef,
+                        const double* acc, float count, const void* w_packed_t, void* dx, int lddx, int dx_accumulate,
+                        const DySegs* dxs, int n, int h, int w, int cin, int cout, hipStream_t stream);
 /* The stem Conv(3 -> 16, k 3, s 2, p 1) of the model YAMLs (nn/modules/conv.py:41-55 as model.0) read straight from the image
  * batch the trainer hands the model (models/yolo/detect/train.py:57-59: fp32 NCHW, img * mul): no import pass, no padded copy.
  * dy_stem_forward writes the raw conv output (N,Ho,Wo,ldraw) fp16 and ADDS the BatchNorm sums into acc [DY_BN_COPIES][2][16]

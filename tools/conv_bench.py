@@ -3,7 +3,9 @@
 usage: conv_bench.py [fwd|wgrad] cin cout ks stride H W [N] [reps]
        conv_bench.py pair cin cout H W [N] [reps]     the backward of one 1x1 Conv + BatchNorm + SiLU stand-alone: the two-launch pair
            (dy_conv_wgrad_bn / _segs, then the input gradient) against the fused launch (dy_conv1x1_wgrad_dgrad_bn / _segs); cin = 64
-           times dX stored and accumulated, cin = 32+32+32 (concatenation members) times the segmented form, members adding alternately"""
+           times dX stored and accumulated, cin = 32+32+32 (concatenation members) times the segmented form, members adding alternately
+       conv_bench.py frozen cin cout H W [N] [reps]   the backward of one FROZEN 1x1 Conv + BatchNorm + SiLU stand-alone: the two-launch form
+           (dy_bn_act_bwd_apply_acc, then the input gradient) against the launch that forms the input gradient alone (dy_conv1x1_dgrad_bn)"""
 import os
 import sys
 
@@ -87,8 +89,73 @@ def pair_bench(argv):
               f"saved {t2 - t1:.1f} us")
 
 
+def frozen_bench(argv):
+    import ctypes as C
+    from ultralytics.hip import DY_ACT_SILU, DY_BN_COPIES, DY_EPI_ACCUM, DySegs
+    parts = tuple(map(int, argv[0].split("+")))
+    cout, H, W = map(int, argv[1:4])
+    N = int(argv[4]) if len(argv) > 4 else 64
+    reps = int(argv[5]) if len(argv) > 5 else 20
+    seg, cin, npix = len(parts) > 1, sum(parts), N * H * W
+    eng = Engine("cuda:0")
+    L = eng.L
+    if not L.dy_conv1x1_dgrad_bn_supported(N, H, W, cin, cout):
+        sys.exit(f"frozen {cin}->{cout} @{H}x{W} n={N}: no input-gradient-only form for this geometry (dy_conv1x1_dgrad_bn_supported)")
+    w = torch.randn(cout, cin, 1, 1, device="cuda") / cin ** 0.5
+    sp = ConvSpec("b", w, None, None, 1, 1, 0)
+    eng.prepare_conv(sp)
+    eng.pack(sp)
+    half = lambda *sh: torch.randn(*sh, device="cuda").half()  # noqa: E731
+    gt = [half(N, H, W, c) for c in parts]
+    dy, raw, draw = half(N, H, W, cout) * 0.05, half(N, H, W, cout), half(N, H, W, cout)
+    coef = torch.cat([torch.rand(cout) + 0.5, torch.randn(cout) * 0.1, torch.randn(cout) * 0.1, torch.rand(cout) + 0.5]).cuda()
+    acc = torch.randn(DY_BN_COPIES, 2, cout, dtype=torch.float64, device="cuda") * npix * 1e-3
+    dg, db = torch.zeros(cout, device="cuda"), torch.zeros(cout, device="cuda")
+    wt = sp.wpack_t.data_ptr()
+
+    def timed(f):
+        for _ in range(3):
+            f()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        torch.cuda.synchronize()
+        ev[0].record()
+        for _ in range(reps):
+            f()
+        ev[1].record()
+        torch.cuda.synchronize()
+        return ev[0].elapsed_time(ev[1]) / reps * 1e3
+
+    apply = lambda: eng.call("dy_bn_act_bwd_apply_acc", dy.data_ptr(), cout, raw.data_ptr(), cout, draw.data_ptr(), cout, coef.data_ptr(),  # noqa: E731
+                             acc.data_ptr(), dg.data_ptr(), db.data_ptr(), npix, cout, DY_ACT_SILU, float(npix))
+    forms = [("segmented", [i % 2 for i in range(len(parts))])] if seg else [("store", 0), ("accumulate", 1)]
+    for tag, a in forms:
+        if seg:
+            dxs, end = DySegs(), 0
+            dxs.nseg = len(parts)
+            for i, c in enumerate(parts):
+                end += c
+                dxs.c_end[i], dxs.ld[i], dxs.ptr[i], dxs.acc[i] = end, c, gt[i].data_ptr(), a[i]
+            two = lambda: (apply(), eng.call("dy_conv1x1_input_grad_segs", draw.data_ptr(), cout, wt, C.byref(dxs), N, H, W, cout, cin))  # noqa: E731
+            one = lambda: eng.call("dy_conv1x1_dgrad_bn", dy.data_ptr(), 0, cout, 0, raw.data_ptr(), cout, coef.data_ptr(), acc.data_ptr(), float(npix),  # noqa: E731
+                                   wt, 0, 0, 0, C.byref(dxs), N, H, W, cin, cout)
+            old = sum(c for c, f in zip(parts, a) if f)
+        else:
+            two = lambda: (apply(), eng.call("dy_conv_forward", draw.data_ptr(), cout, wt, 0, gt[0].data_ptr(), cin, 0, N, H, W, cout, cin, 1, 1, 1,  # noqa: E731
+                                             H, W, DY_EPI_ACCUM if a else 0, None))
+            one = lambda: eng.call("dy_conv1x1_dgrad_bn", dy.data_ptr(), 0, cout, 0, raw.data_ptr(), cout, coef.data_ptr(), acc.data_ptr(), float(npix),  # noqa: E731
+                                   wt, gt[0].data_ptr(), cin, a, None, N, H, W, cin, cout)
+            old = cin if a else 0
+        t2, t1 = timed(two), timed(one)
+        b2, b1 = npix * (cin + 4 * cout + old) * 2, npix * (cin + 2 * cout + old) * 2  # own bytes: the pair also writes and reads d(raw)
+        print(f"frozen {argv[0]}->{cout} @{H}x{W} n={N} {tag}: apply + input gradient {t2:.1f} us ({b2 / t2 / 1e6:.2f} TB/s)  one launch {t1:.1f} us "
+              f"({b1 / t1 / 1e6:.2f} TB/s)  saved {t2 - t1:.1f} us", flush=True)
+
+
 if sys.argv[1] == "pair":
     pair_bench(sys.argv[2:])
+    sys.exit(0)
+if sys.argv[1] == "frozen":
+    frozen_bench(sys.argv[2:])
     sys.exit(0)
 mode, cin, cout, ks, s, H, W = sys.argv[1], *map(int, sys.argv[2:8])
 N = int(sys.argv[8]) if len(sys.argv) > 8 else 64
