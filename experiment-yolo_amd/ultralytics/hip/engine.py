@@ -1529,6 +1529,24 @@ class Engine:
         self._record(self._live(None, x), y, bwd)
         return y
 
+    def space_to_depth(self, x: Act, out: Act | None = None):
+        """SPDConv's rearrangement (reference nn/extra_modules/block.py:2504-2507): (N, H, W, C) -> (N, H/2, W/2, 4C), channel group
+        a + 2b holding the pixels of row parity a and column parity b.  A permutation, so the backward is the same launch the other
+        way; an input that needs no gradient (a frozen prefix) leaves nothing on the tape."""
+        x = self.dense(x)
+        if x.H % 2 or x.W % 2 or x.H < 2 or x.W < 2:
+            raise ValueError(f"space-to-depth needs an even map, got {x.H}x{x.W}")
+        y = out if out is not None else self.new_act(x.N, x.H // 2, x.W // 2, 4 * x.C)
+        assert (y.N, y.H, y.W, y.C) == (x.N, x.H // 2, x.W // 2, 4 * x.C)
+        self._use(x)
+        self.call("dy_space_to_depth", x.ptr, x.ld, y.ptr, y.ld, x.N, x.H, x.W, x.C, 0, 0)
+
+        def bwd():
+            acc = x.grad_target()
+            self.call("dy_space_to_depth", x.gptr, x.ld, y.gptr, y.ld, x.N, x.H, x.W, x.C, 1, acc)
+        self._record(self._live(None, x), y, bwd)
+        return y
+
     def maxpool5(self, x: Act, out: Act):
         x = self.dense(x)
         arg = self.transient((x.npix * x.C,), torch.uint8)

@@ -1,5 +1,5 @@
 """Attentional scale-sequence fusion blocks: Zoom_cat, ScalSeq, Add (drop-in for reference
-nn/extra_modules/block.py:3402-3484)."""
+nn/extra_modules/block.py:3402-3484), and SPDConv, the space-to-depth down-sampling layer (reference :2497-2507)."""
 from __future__ import annotations
 
 import torch
@@ -10,7 +10,7 @@ from ...hip.engine import BN3D_EPS, BN3D_MOM
 from ...hip.runtime import HipModule
 from ..modules.conv import Conv
 
-__all__ = ("Zoom_cat", "ScalSeq", "Add")
+__all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv")
 
 
 class Zoom_cat(HipModule):
@@ -59,3 +59,24 @@ class Add(HipModule):
 
     def forward_act(self, xs, out=None):
         return self.rt.eng.add(list(xs), out)
+
+
+class SPDConv(HipModule):
+    """Space-to-depth convolution (reference :2497-2507): the four pixels of every 2x2 block become four channel groups
+    (``cat([x[..., ::2, ::2], x[..., 1::2, ::2], x[..., ::2, 1::2], x[..., 1::2, 1::2]], 1)``), then Conv(4 * inc, ouc, k=3) -- a
+    down-sampling layer that drops no pixel.  The rearrangement is one permutation launch (csrc/spd.hip); the convolution is the
+    ordinary 3x3 path on the 4 * inc-channel tensor, its weights in ``state_dict`` order."""
+
+    def __init__(self, inc, ouc, dimension=1):
+        super().__init__()
+        self.d = dimension
+        self.conv = Conv(inc * 4, ouc, k=3)
+
+    def out_hw(self, h, w):
+        return h // 2, w // 2
+
+    def forward_act(self, x, out=None):
+        if x.H % 2 or x.W % 2 or x.H < 2 or x.W < 2:
+            raise ValueError(f"SPDConv (layer {getattr(self, 'i', '?')}) needs a map with even sides, got {x.H}x{x.W}: "
+                             "the reference's torch.cat of the four parity views fails on it too")
+        return self.conv.forward_act(self.rt.eng.space_to_depth(x), out)

@@ -20,7 +20,7 @@ import yaml
 
 from ..hip.engine import Act
 from ..hip.runtime import HipModule, Runtime
-from .extra_modules.block import Add, ScalSeq, Zoom_cat
+from .extra_modules.block import Add, ScalSeq, SPDConv, Zoom_cat
 from .modules import SPPF, C2f, Concat, Conv, Detect, LDConv
 
 CFG_MODELS = Path(__file__).resolve().parent.parent / "cfg" / "models"
@@ -44,7 +44,7 @@ class Upsample(HipModule):
 
 
 _MODULES = {"Conv": Conv, "LDConv": LDConv, "C2f": C2f, "SPPF": SPPF, "Concat": Concat, "nn.Upsample": Upsample,
-            "ScalSeq": ScalSeq, "Add": Add, "Zoom_cat": Zoom_cat, "Detect": Detect}
+            "ScalSeq": ScalSeq, "Add": Add, "Zoom_cat": Zoom_cat, "Detect": Detect, "SPDConv": SPDConv}
 
 
 def guess_model_scale(model_path):
@@ -71,7 +71,7 @@ def yaml_model_load(path):
 
 def parse_model(d, ch, verbose=True):
     """YAML dict -> (nn.Sequential, savelist, per-layer down-sampling) for the hot-path module names
-    (reference tasks.py:780-1062, branches :825-864, :905-911, :1001-1008)."""
+    (reference tasks.py:780-1062, branches :825-864 -- SPDConv is in that list at :833 --, :905-911, :1001-1008)."""
     nc, scales = d.get("nc"), d.get("scales")
     depth, width, max_channels = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0), float("inf")
     if scales:
@@ -86,7 +86,7 @@ def parse_model(d, ch, verbose=True):
         args = [nc if a == "nc" else (None if a == "None" else a) for a in args]
         n_ = n = max(round(n * depth), 1) if n > 1 else n
         fl = [f] if isinstance(f, int) else list(f)
-        if m in (Conv, LDConv, C2f, SPPF):
+        if m in (Conv, LDConv, C2f, SPPF, SPDConv):
             c1, c2 = chs[f], args[0]
             if c2 != nc:
                 c2 = make_divisible(min(c2, max_channels) * width, 8)
@@ -94,7 +94,7 @@ def parse_model(d, ch, verbose=True):
             if m is C2f:
                 args.insert(2, n)
                 n = 1
-            s = args[3] if (m in (Conv, LDConv) and len(args) > 3) else 1
+            s = 2 if m is SPDConv else args[3] if (m in (Conv, LDConv) and len(args) > 3) else 1
             ds = down[f] * s
         elif m is Upsample:
             c2, ds = chs[f], down[f] / int(args[1])
@@ -173,7 +173,7 @@ class BaseModel(HipModule):
                 fl = [m.i + j if j < 0 else j for j in m.f]
                 if len(set(fl)) != len(fl) or any(j in plan for j in fl):
                     continue
-                ok = all(isinstance(self.model[j], (Conv, LDConv, C2f, SPPF, Upsample, Add, ScalSeq)) for j in fl)
+                ok = all(isinstance(self.model[j], (Conv, LDConv, C2f, SPPF, SPDConv, Upsample, Add, ScalSeq)) for j in fl)
                 if ok:
                     for pos, j in enumerate(fl):
                         plan[j] = (m.i, pos)
@@ -403,6 +403,8 @@ class DetectionModel(BaseModel):
                 out.append(m.conv.out_channels)
             elif isinstance(m, LDConv):
                 out.append(m.conv[0].out_channels)
+            elif isinstance(m, SPDConv):
+                out.append(m.conv.conv.out_channels)
             elif isinstance(m, (C2f, SPPF)):
                 out.append(m.cv2.conv.out_channels)
             elif isinstance(m, Upsample):

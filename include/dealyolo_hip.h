@@ -329,6 +329,14 @@ int dy_add(const void* a, int lda, const void* b, int ldb, const void* c, int ld
            hipStream_t stream);
 int dy_upsample2x(const void* x, int ldx, void* y, int ldy, int n, int h, int w, int C, int backward, int accumulate,
                   hipStream_t stream);
+/* SPDConv's space-to-depth, nn/extra_modules/block.py:2504-2507 (``torch.cat([x[..., ::2, ::2], x[..., 1::2, ::2], x[..., ::2, 1::2],
+ * x[..., 1::2, 1::2]], 1)`` in front of its 3x3 Conv): y[n, i, j, (a + 2b) C + k] = x[n, 2i + a, 2j + b, k] with a the row and b the
+ * column parity.  x: (n, h, w, C) at pixel stride ldx; y: (n, h/2, w/2, 4C) at pixel stride ldy; either may be a channel slice of a
+ * wider tensor, and no other channel is touched.  backward = 0: y <- x.  backward = 1: y holds dY and x receives dX (accumulate = 1:
+ * is added to, one fp16 addition per element).  DY_ERR_ARG for a null pointer or an odd / < 2 map side, DY_ERR_ALIGN when C, ldx or
+ * ldy is no multiple of 8 or a pointer is not 16-byte aligned; nothing is launched then. */
+int dy_space_to_depth(void* x, int ldx, void* y, int ldy, int n, int h, int w, int C, int backward, int accumulate,
+                      hipStream_t stream);
 int dy_maxpool5(const void* x, int ldx, void* y, int ldy, void* argmax, int n, int h, int w, int C, hipStream_t stream);
 int dy_maxpool5_backward(const void* dy, int lddy, const void* argmax, void* dx, int lddx, int n, int h, int w, int C,
                          int accumulate, hipStream_t stream);
