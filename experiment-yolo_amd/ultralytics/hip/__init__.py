@@ -191,6 +191,7 @@ SIGNATURES = {
     "dy_axpy_f32": (i32, [vp, vp, f32, i64, vp]),
     "dy_scale_img": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "dy_tta_merge": (i32, [i32, C.POINTER(vp), ip, ip, ip, C.POINTER(f32), ip, i32, i32, i32, i32, vp, vp]),
+    "dy_bootstrap_ap": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
 }
 
 _LIB = None

@@ -582,6 +582,19 @@ int dy_scale_img(const float* x, int B, int H, int W, int flip, int Ho, int Wo, 
 int dy_tta_merge(int n_pass, const float* const* y_ptrs, const int* A, const int* col_lo, const int* col_hi, const float* scale,
                  const int* flip, int B, int no, int H, int W, float* out, hipStream_t stream);
 
+/* ---- paired bootstrap of the validation statistics, reference testandcox.py:150-227 (30 resamples of the test split, one full
+ *      ``model.val`` per resample and model) with ultralytics/utils/metrics.py compute_ap (:1109-1139) / ap_per_class (:1142-1230):
+ *      AP of every (resample, class, IoU threshold) from ONE validation pass in one launch, one workgroup per (resample, class).
+ * Per model, prepared once: the D detections sorted by (class, confidence descending, stable) -- tp_bits[d] bit j = true positive at
+ * IoU threshold j of the validator's ten, det_img[d] = image index -- cls_off (nc + 1) = the class segments of that order, lab_cnt
+ * (n_img, nc) = labels per image and class.  Per call: mult (S, n_img) uint16 = how often image i occurs in resample s.
+ * ap (S, nc, 10) fp64 = what compute_ap returns for the list in which every detection of image i appears mult[s, i] times (recall =
+ * tpc / (n_l + 1e-16), sentinels (0, 1) / (1, 0), right-to-left envelope, np.interp on linspace(0, 1, 101), trapezoid); 0 where the
+ * class has no label or no detection in the resample.  nl (S, nc) = sum_i mult[s, i] * lab_cnt[i, c].  No workspace: nothing of size
+ * D or S x D is written.  The weighted detections of one class and resample must stay below 2^31 (callers check on the host). */
+int dy_bootstrap_ap(const unsigned short* tp_bits, const int* det_img, const int* cls_off, const int* lab_cnt,
+                    const unsigned short* mult, int D, int n_img, int nc, int S, double* ap, int* nl, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
