@@ -192,6 +192,8 @@ SIGNATURES = {
     "dy_scale_img": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "dy_tta_merge": (i32, [i32, C.POINTER(vp), ip, ip, ip, C.POINTER(f32), ip, i32, i32, i32, i32, vp, vp]),
     "dy_bootstrap_ap": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+    "dy_confusion_matrix": (i32, [vp, vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, f32, i32, vp, vp, vp]),
+    "dy_count_fp": (i32, [vp, vp, vp, vp, vp, i32, f32, C.c_double, vp, vp, vp]),
 }
 
 _LIB = None

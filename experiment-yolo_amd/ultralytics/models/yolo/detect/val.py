@@ -1,8 +1,9 @@
 """DetectionValidator with the reference's method names (reference models/yolo/detect/val.py, engine/validator.py).
 
 ``update_metrics`` handles a whole batch with ONE launch of dy_match_predictions (label/prediction rescaling, IoU, greedy
-matching at the ten IoU thresholds); the statistics stay on the device until ``get_stats``.  Dataset construction, JSON /
-txt dumps, plots and the confusion matrix are control plane or data pipeline."""
+matching at the ten IoU thresholds); the statistics stay on the device until ``get_stats``.  With ``args.plots`` (the reference's
+gate, val.py:136) one launch of dy_confusion_matrix per batch adds the batch to ``confusion_matrix`` from the same native-space
+predictions.  Dataset construction, JSON / txt dumps and plots are control plane or data pipeline."""
 import ctypes as C
 
 import numpy as np
@@ -10,7 +11,7 @@ import torch
 
 from ....hip import check, lib
 from ....utils import LOGGER, ops
-from ....utils.metrics import DetMetrics
+from ....utils.metrics import ConfusionMatrix, DetMetrics
 from ....hip.engine import dev_empty
 
 
@@ -24,6 +25,7 @@ class DetectionValidator:
         self.iouv = torch.linspace(0.5, 0.95, 10)  # mAP@0.5:0.95 thresholds (reference val.py:37)
         self.niou = self.iouv.numel()
         self.metrics = DetMetrics()
+        self.confusion_matrix = None
         self.stats = dict(tp=[], conf=[], pred_cls=[], target_cls=[])
         self.training = False
 
@@ -35,6 +37,7 @@ class DetectionValidator:
         self.metrics.names = self.names
         self.seen = 0
         self.stats = dict(tp=[], conf=[], pred_cls=[], target_cls=[])
+        self.confusion_matrix = ConfusionMatrix(nc=self.nc, conf=self.args.conf).zero_(self.device)  # reference val.py:75
 
     def preprocess(self, batch):
         dev = self.device
@@ -82,9 +85,12 @@ class DetectionValidator:
         tbox = batch["bboxes"].reshape(-1, 4).float().contiguous()
         tp = torch.zeros((ntot, self.niou), dtype=torch.uint8, device=dev)
         predn = dev_empty((ntot, 6), torch.float32, dev)
-        if ntot:
+        ntgt = tcls.numel()
+        confusion = bool(self.args.plots and self.nc >= 1 and (ntot or ntgt))  # reference val.py:136; nothing to count in an empty batch
+        if ntot or confusion:
             geom = torch.from_numpy(self._geometry(batch, B, imgsz)).to(dev)
             offd = torch.from_numpy(off).to(dev)
+        if ntot:
             if getattr(self, "_status", None) is None or self._status.device != dev:
                 self._status = torch.zeros(1, dtype=torch.int32, device=dev)  # ONE word for the whole run: every batch ORs into it
             status = self._status
@@ -93,6 +99,11 @@ class DetectionValidator:
                                              tcls.numel(), geom.data_ptr(), iouv.data_ptr(), self.niou, B, imgsz[0], imgsz[1],
                                              tp.data_ptr(), predn.data_ptr(), status.data_ptr(),
                                              torch.cuda.current_stream(dev).cuda_stream), "dy_match_predictions")
+        if confusion:  # labelled images only (val.py:131-152 never hands an unlabelled one over); no synchronisation
+            if self.confusion_matrix is None or self.confusion_matrix.nc != self.nc:
+                self.confusion_matrix = ConfusionMatrix(nc=self.nc, conf=self.args.conf)
+            self.confusion_matrix.launch(predn.data_ptr() if ntot else 0, offd.data_ptr(), ntot, tidx.data_ptr() if ntgt else 0,
+                                         tcls.data_ptr() if ntgt else 0, tbox.data_ptr() if ntgt else 0, ntgt, geom.data_ptr(), B, imgsz, True, dev)
         self.seen += B
         # images with neither predictions nor labels contribute nothing; label-only images contribute their target classes
         self.stats["tp"].append(tp.bool())
@@ -106,10 +117,13 @@ class DetectionValidator:
         if getattr(self, "_status", None) is not None and int(self._status.item()) & 1:
             self._status.zero_()
             raise RuntimeError("an image carried more than 1024 labels (dy_match_predictions capacity)")
+        if self.confusion_matrix is not None and self.confusion_matrix.status() & 1:
+            raise RuntimeError("an image carried more than 1024 labels (dy_confusion_matrix capacity)")
         stats = {k: torch.cat(v, 0).cpu().numpy() for k, v in self.stats.items() if len(v)}
         if len(stats) and stats["tp"].any():
             self.metrics.process(**stats)
         self.nt_per_class = np.bincount(stats["target_cls"].astype(int), minlength=self.nc) if len(stats) else np.zeros(self.nc, int)
+        self.metrics.confusion_matrix = self.confusion_matrix  # reference val.py:166
         return self.metrics.results_dict
 
     def print_results(self):

@@ -3,7 +3,9 @@
 ``box_iou`` runs on the GPU (libdealyolo_hip: dy_box_iou); the per-batch matching lives in
 ``ultralytics.models.yolo.detect.DetectionValidator`` (dy_match_predictions).  ``ap_per_class`` / ``compute_ap`` / ``smooth``
 and the ``Metric`` / ``DetMetrics`` containers are host arithmetic in the reference as well (numpy on the concatenated
-statistics, utils/metrics.py:1051-1480) and stay host arithmetic here; plotting and the confusion matrix are control plane.
+statistics, utils/metrics.py:1051-1480) and stay host arithmetic here.  ``ConfusionMatrix`` counts on the device (dy_confusion_matrix:
+one launch per batch from the validator, one per ``process_batch`` call) and is read back when ``.matrix`` is asked for; plotting is
+control plane.
 """
 import ctypes as C
 
@@ -73,6 +75,87 @@ def ap_per_class(tp, conf, pred_cls, target_cls, plot=False, on_plot=None, save_
     return tpn, fpn, p, r, f1, ap, classes.astype(int), p_curve, r_curve, f1_curve, x, np.array([])
 
 
+class ConfusionMatrix:
+    """Detection confusion matrix (reference :903-997) counted on the device.  ``matrix[predicted, true]`` with index ``nc`` =
+    background, an (nc+1, nc+1) float64 array read back from the int32 device counter on access.  ``process_batch`` takes one image
+    (reference :935-986); ``DetectionValidator.update_metrics`` adds a whole batch to the same counter in one launch.  The matching
+    rule, its tie order and the reference's ``if n:`` quirk: csrc/confusion.hip, DESIGN.md."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45, task="detect"):
+        if task != "detect":
+            raise NotImplementedError("ConfusionMatrix: only task='detect' (classification is out of scope, SURVEY.md section 8)")
+        self.task, self.nc = task, int(nc)
+        self.conf = 0.25 if conf in (None, 0.001) else conf  # the default validation confidence means 0.25 (reference :920)
+        self.iou_thres = iou_thres
+        self._buf = None  # (nc+1)^2 counters + one status word, int32, on the device that first uses it
+
+    def counter(self, device):
+        """The device counter (created and zeroed on first use); ``[-1]`` is the kernel's status word."""
+        device = torch.device(device)
+        if self._buf is None:
+            self._buf = torch.zeros((self.nc + 1) ** 2 + 1, dtype=torch.int32, device=device)
+        elif self._buf.device != device:
+            raise RuntimeError(f"ConfusionMatrix counts on {self._buf.device}, got tensors on {device}")
+        return self._buf
+
+    def zero_(self, device=None):
+        if self._buf is not None:
+            self._buf.zero_()
+        elif device is not None:
+            self.counter(device)
+        return self
+
+    def launch(self, predn, pred_off, n_preds, t_bidx, t_cls, t_boxes, n_targets, geom, B, imgsz, skip_unlabelled, device):
+        """One dy_confusion_matrix launch on the current stream; pointers as ints (0 = NULL).  No synchronisation."""
+        buf = self.counter(device)
+        check(lib().dy_confusion_matrix(predn, pred_off, n_preds, t_bidx, t_cls, t_boxes, n_targets, geom, B, imgsz[0], imgsz[1], self.nc,
+                                        self.conf, self.iou_thres, int(skip_unlabelled), buf.data_ptr(), buf.data_ptr() + 4 * (buf.numel() - 1),
+                                        torch.cuda.current_stream(buf.device).cuda_stream), "dy_confusion_matrix")
+
+    def status(self):
+        """The kernel's status word (synchronises): bit 0 = an image had more than 1024 labels, bit 1 = a class outside [0, nc)."""
+        return 0 if self._buf is None else int(self._buf[-1].item())
+
+    def process_batch(self, detections, gt_bboxes, gt_cls):
+        """One image: detections (N,6) x1 y1 x2 y2 conf cls or None, gt_bboxes (M,4) native xyxy, gt_cls (M); CUDA tensors only."""
+        if gt_cls.device.type != "cuda" or (detections is not None and detections.device.type != "cuda"):
+            raise RuntimeError("ConfusionMatrix.process_batch: HIP path only (no CPU fallback)")
+        det = detections.reshape(-1, 6).float().contiguous() if detections is not None else None
+        box, cls = gt_bboxes.reshape(-1, 4).float().contiguous(), gt_cls.reshape(-1).float().contiguous()
+        nd, nl = (det.shape[0] if det is not None else 0), cls.shape[0]
+        self.launch(det.data_ptr() if nd else 0, 0, nd, 0, cls.data_ptr() if nl else 0, box.data_ptr() if nl else 0, nl, 0, 1, (0, 0), False,
+                    gt_cls.device)
+
+    @property
+    def matrix(self):
+        n = self.nc + 1
+        if self._buf is None:
+            return np.zeros((n, n))
+        host = self._buf.cpu().numpy()
+        if host[-1] & 1:
+            raise RuntimeError("an image carried more than 1024 labels (dy_confusion_matrix capacity)")
+        if host[-1] & 2:
+            raise RuntimeError(f"a detection or label class lies outside [0, {self.nc}) (dy_confusion_matrix)")
+        return host[:-1].reshape(n, n).astype(np.float64)
+
+    def tp_fp(self):
+        """True and false positives per class, background dropped (reference :992-997)."""
+        m = self.matrix
+        tp = m.diagonal()
+        return tp[:-1], (m.sum(1) - tp)[:-1]
+
+    def print(self):
+        m = self.matrix
+        for i in range(self.nc + 1):
+            print(" ".join(map(str, m[i])))
+
+    def process_cls_preds(self, preds, targets):
+        raise NotImplementedError("ConfusionMatrix: classification is out of scope (SURVEY.md section 8)")
+
+    def plot(self, *args, **kwargs):
+        raise NotImplementedError("confusion-matrix plotting is control plane (SURVEY.md section 8: out of scope)")
+
+
 def _avg(a, empty=0.0):
     return a.mean() if len(a) else empty
 
@@ -123,6 +206,7 @@ class DetMetrics:
     def __init__(self, save_dir=None, plot=False, on_plot=None, names=()):
         self.save_dir, self.plot, self.on_plot, self.names = save_dir, plot, on_plot, names
         self.box = Metric()
+        self.confusion_matrix = None  # the validator's ConfusionMatrix after get_stats (reference val.py:166)
         self.speed = dict.fromkeys(("preprocess", "inference", "loss", "postprocess"), 0.0)
 
     def process(self, tp, conf, pred_cls, target_cls):

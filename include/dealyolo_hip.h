@@ -595,6 +595,30 @@ int dy_tta_merge(int n_pass, const float* const* y_ptrs, const int* A, const int
 int dy_bootstrap_ap(const unsigned short* tp_bits, const int* det_img, const int* cls_off, const int* lab_cnt,
                     const unsigned short* mult, int D, int n_img, int nc, int S, double* ap, int* nl, hipStream_t stream);
 
+/* ---- detection confusion matrix, reference ultralytics/utils/metrics.py:935-986 (ConfusionMatrix.process_batch; box_iou :53-73), as
+ *      the reference validator fills it per labelled image (models/yolo/detect/val.py:136-152), for a whole batch in ONE launch, one
+ *      workgroup per image.  predn (n_preds,6) native-space x1 y1 x2 y2 conf cls with pred_off (B+1): what dy_match_predictions writes;
+ *      targets and geom as dy_match_predictions takes them (same native-space formulas).  geom NULL: t_boxes are native xyxy already.
+ *      pred_off NULL / t_batch_idx NULL (B == 1 only): the one image owns all n_preds detections / all n_targets labels.
+ * Rule: detections with conf > conf_thr each choose the label of largest IoU among IoU > iou_thres (any class); a label keeps the
+ * chooser of largest IoU.  matrix (nc+1,nc+1) int32, [predicted, true], index nc = background, is ADDED to (caller zeroes it): a
+ * label with a winner -> [cls(winner), cls(label)], without -> [nc, cls(label)]; only if the image has a matched pair (the
+ * reference's ``if n:``, :983), every other kept detection -> [cls(det), nc].  An image without labels adds nothing when
+ * skip_unlabelled (the validator), else its kept detections -> [cls, nc] (:945-951).  Exact IoU ties, undefined in the reference
+ * (unstable argsort), go to the lower label index, then the lower detection index.
+ * *status |= 1 if an image has > 1024 labels, |= 2 if a class lies outside [0, nc) (that entry is not counted). */
+int dy_confusion_matrix(const float* predn, const int* pred_off, int n_preds, const float* t_batch_idx, const float* t_cls,
+                        const float* t_boxes, int n_targets, const float* geom, int B, int img_h, int img_w, int nc, float conf_thr,
+                        float iou_thres, int skip_unlabelled, int* matrix, int* status, hipStream_t stream);
+/* ---- false-positive count, reference gt_fails.py:35-84 (count_fp with load_labels :9-16, yolo_to_xyxy :18-23, iou :25-33), for a
+ *      batch of images in one launch, one wave per image.  dets (Ntot,6) native pixels with det_off (B+1); labels (Ltot,5) fp64 rows
+ *      cls xc yc w h in file order with lab_off (B+1); wh (B,2) image width, height.  Detections with conf >= conf_thr, in stored
+ *      order, each take the FIRST unused label of the same class with inter / (area_a + area_b - inter + 1e-6) >= iou_thr (labels
+ *      xc*w -+ bw*w/2, unclipped); fp[b] = detections that found none.  The script's mix of float32 and float64 is replaced by fp64
+ *      arithmetic on the fp32 detections: equal away from the threshold.  *status |= 1 if an image has > 1024 labels. */
+int dy_count_fp(const float* dets, const int* det_off, const double* labels, const int* lab_off, const int* wh, int B, float conf_thr,
+                double iou_thr, int* fp, int* status, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
