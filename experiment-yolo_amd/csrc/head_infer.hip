@@ -33,6 +33,23 @@ struct HeadInferArgs {
   float* y;           // (B, 4 + nc, A)
   int nl, B, A, nc, cin_c;
 };
+// LOGITS instantiations (dy_head_infer_levels_logits) also write what the eager final convs would: per level the fp32 box logits
+// [npix][64] and class logits [npix][ncp] (ncp = nc rounded up to 8, channels [nc, ncp) exact zeros).  The plain kernel's argument
+// block is HeadInferArgs alone, as before.
+struct HeadInferLogits {
+  float* box[4];
+  float* cls[4];
+  int ncp;
+};
+template <bool LOGITS>
+struct HeadInferPack {
+  HeadInferArgs g;
+};
+template <>
+struct HeadInferPack<true> {
+  HeadInferArgs g;
+  HeadInferLogits o;
+};
 
 // 4 x 4 transpose across the four 16-lane rows of a wave and four registers: (register t, row q) -> (register q, row t), two
 // v_permlane32_swap + two v_permlane16_swap (gfx950).  The MFMA result layout gives a lane the channels of ITS row for one pixel of
@@ -56,8 +73,9 @@ static __device__ __forceinline__ void xpose4(float& r0, float& r1, float& r2, f
 
 // CCK: channels per k-step of the class conv (32, or 16 = half of every MFMA's K is zero padding -- what dy_conv_forward does for
 // channel counts like 48 / 80); KS: k-steps; MT: 16-row tiles of class outputs.
-template <int CCK, int KS, int MT>
-__global__ __launch_bounds__(256, 2) void head_infer_kernel(HeadInferArgs g) {
+template <int CCK, int KS, int MT, bool LOGITS>
+__global__ __launch_bounds__(256, 2) void head_infer_kernel(HeadInferPack<LOGITS> k) {
+  const HeadInferArgs& g = k.g;
   const HeadInferLevel& a = g.lv[blockIdx.y];
   if ((int)blockIdx.x >= a.nblk) return;
   constexpr int PB = 160;                 // box weight row pitch (bytes): 10 slots, == 2 mod 4 (conflict-free ds_read_b128 groups)
@@ -127,6 +145,13 @@ __global__ __launch_bounds__(256, 2) void head_infer_kernel(HeadInferArgs g) {
         for (int m = 0; m < 4; ++m)
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[m * 4 + j] = acc[m][t][j] + s_bb[q * 16 + m * 4 + j];
+        if constexpr (LOGITS) {  // v[0..16) = channels 16 q .. 16 q + 15 of this pixel: 64 contiguous bytes
+          if (pix < npix) {
+            f32x4* const d = reinterpret_cast<f32x4*>(k.o.box[blockIdx.y] + pix * 64 + q * 16);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) d[m] = (f32x4){v[m * 4], v[m * 4 + 1], v[m * 4 + 2], v[m * 4 + 3]};
+          }
+        }
         float mx = v[0];
 #pragma unroll
         for (int k = 1; k < 16; ++k) mx = fmaxf(mx, v[k]);
@@ -181,6 +206,18 @@ __global__ __launch_bounds__(256, 2) void head_infer_kernel(HeadInferArgs g) {
 #pragma unroll
           for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf[t][ks], acc[t], 0, 0, 0);
         }
+        if constexpr (LOGITS) {  // acc[t][0..4) + bias = channels 16 m + 4 q .. + 3 of pixel base + 16 t + p: 16 contiguous bytes
+          const int c0 = m * 16 + q * 4;  // (rows >= nc carry zero weights and a zero bias: the padding channels come out as exact zeros)
+          if (c0 < k.o.ncp) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+              const long pix = base + t * 16 + p;
+              if (pix < npix)
+                *reinterpret_cast<f32x4*>(k.o.cls[blockIdx.y] + pix * k.o.ncp + c0) =
+                    (f32x4){acc[t][0] + s_bc[c0], acc[t][1] + s_bc[c0 + 1], acc[t][2] + s_bc[c0 + 2], acc[t][3] + s_bc[c0 + 3]};
+            }
+          }
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const float bj = s_bc[m * 16 + q * 4 + j];
@@ -211,10 +248,10 @@ extern "C" int dy_head_infer_supported(int cin_box, int cout_box, int cin_cls, i
   return (cin_box == 64 && cout_box == 64 && nc >= 1 && nc <= 80 && head_infer_shape(cin_cls, &cck, &ks)) ? 1 : 0;
 }
 
-template <int CCK, int KS>
-static int head_infer_mt(int mt, dim3 grid, size_t lds, hipStream_t s, const HeadInferArgs& g) {
+template <int CCK, int KS, bool LOGITS>
+static int head_infer_mt(int mt, dim3 grid, size_t lds, hipStream_t s, const HeadInferPack<LOGITS>& g) {
   switch (mt) {
-#define DY_MT(M) case M: { static bool set = false; auto k = head_infer_kernel<CCK, KS, M>; \
+#define DY_MT(M) case M: { static bool set = false; auto k = head_infer_kernel<CCK, KS, M, LOGITS>; \
     if (!set) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess) return DY_ERR_LAUNCH; set = true; } \
     hipLaunchKernelGGL(k, grid, dim3(256), lds, s, g); break; }
     DY_MT(1) DY_MT(2) DY_MT(3) DY_MT(4) DY_MT(5)
@@ -225,17 +262,25 @@ static int head_infer_mt(int mt, dim3 grid, size_t lds, hipStream_t s, const Hea
   return DY_OK;
 }
 
-extern "C" int dy_head_infer_levels(int nl, const void* const* x_box, const int* ld_box, const float* const* w_box, const float* const* b_box,
-                                    const void* const* x_cls, const int* ld_cls, const float* const* w_cls, const float* const* b_cls,
-                                    const int* h, const int* w, const float* stride, int n, int cin_cls, int nc, float* y,
-                                    hipStream_t stream) {
+template <bool LOGITS>
+static int head_infer_launch(int nl, const void* const* x_box, const int* ld_box, const float* const* w_box, const float* const* b_box,
+                             const void* const* x_cls, const int* ld_cls, const float* const* w_cls, const float* const* b_cls,
+                             const int* h, const int* w, const float* stride, int n, int cin_cls, int nc, float* y,
+                             float* const* box_logits, float* const* cls_logits, hipStream_t stream) {
   int cck, ks;
   if (nl < 1 || nl > 4 || n < 1 || !y || !head_infer_shape(cin_cls, &cck, &ks) || nc < 1 || nc > 80) return DY_ERR_ARG;
-  HeadInferArgs g{};
+  HeadInferPack<LOGITS> pk{};
+  HeadInferArgs& g = pk.g;
   int a0 = 0, gx = 1;
   for (int l = 0; l < nl; ++l) {
     if (!x_box[l] || !x_cls[l] || !w_box[l] || !b_box[l] || !w_cls[l] || !b_cls[l] || h[l] < 1 || w[l] < 1) return DY_ERR_ARG;
     if ((ld_box[l] & 7) || (ld_cls[l] & 7) || ((uintptr_t)x_box[l] & 15) || ((uintptr_t)x_cls[l] & 15)) return DY_ERR_ALIGN;
+    if constexpr (LOGITS) {
+      if (!box_logits || !cls_logits || !box_logits[l] || !cls_logits[l]) return DY_ERR_ARG;
+      if (((uintptr_t)box_logits[l] & 15) || ((uintptr_t)cls_logits[l] & 15)) return DY_ERR_ALIGN;  // 16-byte stores; every row pitch is a multiple of 32 bytes
+      pk.o.box[l] = box_logits[l];
+      pk.o.cls[l] = cls_logits[l];
+    }
     // persistent-ish: every workgroup first stages both weight sets as fp16 (4,096 + nc x cin fp32 loads), so a few long-lived workgroups per
     // CU beat one per 256 pixels (DY_HEAD_INFER_WGS: the cap per level)
     static const int cap = getenv("DY_HEAD_INFER_WGS") ? atoi(getenv("DY_HEAD_INFER_WGS")) : 512;  // 4096 / 2048 / 1024 / 512 / 256: 768 / 708 / 673 / 656 / 840 us at 1280x1280, batch 32, nc 80
@@ -247,18 +292,37 @@ extern "C" int dy_head_infer_levels(int nl, const void* const* x_box, const int*
     gx = (int)blocks > gx ? (int)blocks : gx;
   }
   g.y = y; g.nl = nl; g.B = n; g.A = a0; g.nc = nc; g.cin_c = cin_cls;
+  if constexpr (LOGITS) pk.o.ncp = (nc + 7) / 8 * 8;
   const int mt = (nc + 15) / 16;
   const size_t lds = 64 * 160 + (size_t)16 * mt * (ks * 64 + 32) + (64 + 16 * mt) * 4;
   const dim3 grid(gx, nl);
   if (cck == 32) {
-    if (ks == 1) return head_infer_mt<32, 1>(mt, grid, lds, stream, g);
-    if (ks == 2) return head_infer_mt<32, 2>(mt, grid, lds, stream, g);
-    if (ks == 3) return head_infer_mt<32, 3>(mt, grid, lds, stream, g);
-    if (ks == 4) return head_infer_mt<32, 4>(mt, grid, lds, stream, g);
+    if (ks == 1) return head_infer_mt<32, 1, LOGITS>(mt, grid, lds, stream, pk);
+    if (ks == 2) return head_infer_mt<32, 2, LOGITS>(mt, grid, lds, stream, pk);
+    if (ks == 3) return head_infer_mt<32, 3, LOGITS>(mt, grid, lds, stream, pk);
+    if (ks == 4) return head_infer_mt<32, 4, LOGITS>(mt, grid, lds, stream, pk);
   } else {
-    if (ks == 1) return head_infer_mt<16, 1>(mt, grid, lds, stream, g);
-    if (ks == 3) return head_infer_mt<16, 3>(mt, grid, lds, stream, g);
-    if (ks == 5) return head_infer_mt<16, 5>(mt, grid, lds, stream, g);
+    if (ks == 1) return head_infer_mt<16, 1, LOGITS>(mt, grid, lds, stream, pk);
+    if (ks == 3) return head_infer_mt<16, 3, LOGITS>(mt, grid, lds, stream, pk);
+    if (ks == 5) return head_infer_mt<16, 5, LOGITS>(mt, grid, lds, stream, pk);
   }
   return DY_ERR_ARG;
+}
+
+extern "C" int dy_head_infer_levels(int nl, const void* const* x_box, const int* ld_box, const float* const* w_box, const float* const* b_box,
+                                    const void* const* x_cls, const int* ld_cls, const float* const* w_cls, const float* const* b_cls,
+                                    const int* h, const int* w, const float* stride, int n, int cin_cls, int nc, float* y,
+                                    hipStream_t stream) {
+  return head_infer_launch<false>(nl, x_box, ld_box, w_box, b_box, x_cls, ld_cls, w_cls, b_cls, h, w, stride, n, cin_cls, nc, y, nullptr, nullptr,
+                                  stream);
+}
+
+// The same launch, which also hands out the logits it computes on the way: per level the fp32 box logits (B,H,W,64) and class logits
+// (B,H,W,ncp), bit for bit what the eager final convs write (a validation inside training feeds them to the loss).
+extern "C" int dy_head_infer_levels_logits(int nl, const void* const* x_box, const int* ld_box, const float* const* w_box,
+                                           const float* const* b_box, const void* const* x_cls, const int* ld_cls, const float* const* w_cls,
+                                           const float* const* b_cls, const int* h, const int* w, const float* stride, int n, int cin_cls,
+                                           int nc, float* y, float* const* box_logits, float* const* cls_logits, hipStream_t stream) {
+  return head_infer_launch<true>(nl, x_box, ld_box, w_box, b_box, x_cls, ld_cls, w_cls, b_cls, h, w, stride, n, cin_cls, nc, y, box_logits,
+                                 cls_logits, stream);
 }

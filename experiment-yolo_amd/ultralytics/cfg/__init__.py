@@ -18,7 +18,7 @@ CFG_FRACTION_KEYS = ("dropout", "iou", "lr0", "lrf", "momentum", "weight_decay",
                      "label_smoothing", "hsv_h", "hsv_s", "hsv_v", "translate", "scale", "perspective", "flipud", "fliplr",
                      "mosaic", "mixup", "copy_paste", "conf", "fraction", "iou_ratio")
 CFG_INT_KEYS = ("epochs", "patience", "batch", "workers", "seed", "close_mosaic", "max_det", "vid_stride", "nbs", "save_period", "mask_ratio",
-                "nmax")
+                "nmax", "val_period")
 CFG_BOOL_KEYS = ("save", "exist_ok", "verbose", "deterministic", "single_cls", "rect", "cos_lr", "amp", "val", "half",
                  "agnostic_nms", "plots", "wiou", "nwd", "hipgraph", "multi_scale", "overlap_mask", "wiou_inner", "wiou_focaler")
 

@@ -18,7 +18,7 @@ import torch.distributed as dist
 from ..cfg import get_cfg
 from ..hip.train import StepPlan
 from ..utils import LOGGER, RANK
-from ..utils.torch_utils import ModelEMA, init_seeds, select_device
+from ..utils.torch_utils import EarlyStopping, ModelEMA, init_seeds, select_device
 
 
 def frozen_parameter_names(names, freeze):
@@ -52,6 +52,7 @@ class DetectionTrainer:
         self.device = torch.device("cuda", 0) if self.rehearsal else select_device(self.args.device)
         self.plan = self.ema = None
         self.lf = None
+        self.validator = None  # val_period >= 1: what validate() calls after an epoch (train_on_dataset builds it)
 
     # ---- reference build_optimizer 'auto' rule (engine/trainer.py:1133-1144)
     def _optimizer_choice(self, iterations, nc):
@@ -126,7 +127,11 @@ class DetectionTrainer:
     def train_step(self, batch, ni, epoch):
         """One iteration of the hot loop (reference engine/trainer.py:780-815)."""
         a, p = self.args, self.plan
-        lr = [self.lr0 * self.lf(epoch)] * 3
+        # Past the warm-up the reference's lr lags one epoch behind lf(epoch): its LambdaLR starts at last_epoch = start_epoch - 1 and is
+        # stepped at the END of an epoch (engine/trainer.py:734-737, :873), so epoch e trains with lr0 * lf(e - 1).  The warm-up
+        # writes lr0 * lf(e) into the param groups at its last iteration (:790), which holds for the rest of THAT epoch.
+        lagged = not (self.nb * epoch <= self.nw)
+        lr = [self.lr0 * self.lf(max(epoch - 1, 0) if lagged else epoch)] * 3
         mom = self.momentum
         acc = self.accumulate
         if ni <= self.nw:
@@ -243,6 +248,9 @@ class DetectionTrainer:
         self.setup(nb, batch_size, imgsz)
         self.start_epoch = self.resume_training(a.resume) if a.resume else 0
         self.save_dir = self._save_dir()
+        period = int(getattr(a, "val_period", 0) or 0)  # 0: no per-epoch validation (one after the last epoch, train_on_dataset)
+        if period >= 1:
+            self._begin_val_loop()
         hist = []
         for epoch in range(self.start_epoch, a.epochs):
             if getattr(self, "_epoch_hook", None):
@@ -251,10 +259,10 @@ class DetectionTrainer:
             if ds is not None and getattr(ds, "mosaic", 0.0) and epoch == a.epochs - a.close_mosaic:
                 LOGGER.info("Closing dataloader mosaic")  # _close_dataloader_mosaic (engine/trainer.py:772-776, :934-940)
                 ds.mosaic = 0.0  # the affine / HSV / flip draws go on; batches keep their warp records
-            t0, tloss = time.time(), None
+            t0, tloss, lr = time.time(), None, None
             for i, batch in enumerate(loader):
                 ni = i + nb * epoch
-                self.train_step(batch, ni, epoch)
+                lr, _ = self.train_step(batch, ni, epoch)
                 if ni % 256 == 255:  # long epochs: do not wait for the epoch end to notice steps that do not take effect
                     self.plan.check_progress()
                 if log_every and (i % log_every == 0):
@@ -269,9 +277,107 @@ class DetectionTrainer:
             if self.rank == 0:
                 LOGGER.info(f"epoch {epoch + 1}/{a.epochs}  box/cls/dfl {[round(float(x), 4) for x in hist[-1]]}  "
                             f"{nb * batch_size * self.world_size / (time.time() - t0):.1f} img/s")
-                if self.save_dir is not None:  # reference engine/trainer.py:898-923: last.pt after every epoch
+                if period >= 1:
+                    self.lr = {f"lr/pg{j}": float(x) for j, x in enumerate(lr)}  # of the epoch's last iteration (reference :842)
+                    self._end_of_epoch(hist[-1], period)
+                elif self.save_dir is not None:  # reference engine/trainer.py:898-923: last.pt after every epoch
                     self.save_model(self.save_dir / "weights" / "last.pt")
+            if period >= 1:
+                if self.world_size > 1:  # reference :878-883: every rank leaves the loop together
+                    from ..hip.dist import broadcast_flag
+                    self.stop = broadcast_flag(self.stop, 0)
+                if self.stop:
+                    break
+        if period >= 1 and self.rank == 0:
+            self.final_eval()
         return hist
+
+    # ---- the per-epoch loop of reference engine/trainer.py:844-859 (cfg val_period >= 1) ----------------------------------------------
+    loss_names = ("box_loss", "cls_loss", "dfl_loss")
+    metric_keys = ("metrics/precision(B)", "metrics/recall(B)", "metrics/mAP50(B)", "metrics/mAP50-95(B)")
+
+    def label_loss_items(self, loss_items=None, prefix="train"):
+        """reference models/yolo/detect/train.py:100: ``{prefix}/box_loss`` ... keys, with the items rounded to 5 decimals."""
+        keys = [f"{prefix}/{x}" for x in self.loss_names]
+        if loss_items is None:
+            return keys
+        return dict(zip(keys, (round(float(x), 5) for x in loss_items)))
+
+    def _begin_val_loop(self):
+        """State of the loop: early stopping, fitness bookkeeping, results rows.  Until the first validation the metrics are zeros and
+        the fitness is None, as in the reference (engine/trainer.py:727-730)."""
+        a = self.args
+        self.stopper, self.stop = EarlyStopping(patience=a.patience), False
+        self.best_fitness = getattr(self, "best_fitness", None)  # resume_training restored it
+        self.fitness, self.best_epoch = None, None
+        self.metrics = dict.fromkeys([*self.metric_keys, *self.label_loss_items(prefix="val")], 0)
+        self.results = []
+        self.csv = None if self.save_dir is None else self.save_dir / "results.csv"
+        if self.csv is not None and self.csv.exists() and not a.resume:
+            self.csv.unlink()  # a new run into the same folder starts its own curve; a resumed run appends
+
+    def _end_of_epoch(self, train_items, period):
+        """Rank 0, after an epoch, in the reference's order: validate, results row, early stopping, checkpoints."""
+        a, epoch = self.args, self.epoch
+        final = epoch + 1 == a.epochs
+        if (epoch + 1) % period == 0 or final or self.stopper.possible_stop or self.stop:
+            self.metrics, self.fitness = self.validate()
+        self.save_metrics({**self.label_loss_items(train_items), **self.metrics, **self.lr})
+        self.stop |= self.stopper(epoch + 1, self.fitness)
+        if self.save_dir is not None:
+            self.save_checkpoints()
+
+    def validate(self):
+        """reference engine/trainer.py:963-973: the validator on the EMA model in training mode (metrics + val losses, rounded to 5
+        decimals); the fitness is popped and replaces the best one by the reference's rule (none yet, a zero, or strictly smaller)."""
+        if self.validator is None:
+            raise ValueError("val_period >= 1 needs a validator: train(data=<yaml>) builds one, a loader-fed run sets trainer.validator")
+        metrics = dict(self.validator(trainer=self))
+        fitness = metrics.pop("fitness")
+        if not self.best_fitness or self.best_fitness < fitness:
+            self.best_fitness, self.best_epoch = fitness, self.epoch
+        return metrics, fitness
+
+    def save_metrics(self, metrics):
+        """One row of results.csv (reference engine/trainer.py:1021-1027 format: 23-wide right-aligned columns, ``%.5g`` values, the
+        header once): epoch, training means, metrics, val losses, lr/pg0..2.  The same rows stay in ``self.results``; a run without a
+        save directory writes no file."""
+        row = {"epoch": self.epoch + 1, **metrics}
+        self.results.append(row)
+        if self.csv is None:
+            return
+        n = len(row)
+        text = "" if self.csv.exists() else ("%23s," * n % tuple(row)).rstrip(",") + "\n"
+        text += ("%23.5g," * n % tuple(row.values())).rstrip(",") + "\n"
+        with open(self.csv, "a") as f:
+            f.write(text)
+
+    def save_checkpoints(self):
+        """reference engine/trainer.py:918-923: last.pt every epoch, best.pt when this epoch's fitness IS the best one, epoch{N}.pt
+        by the ``save_period`` rule (N = the 0-based epoch, never epoch 0).  best.pt belongs to the epoch whose validation SET the
+        best fitness: a later epoch that merely ties it, or an epoch without a validation that still carries the stale fitness,
+        leaves best.pt alone (the reference's bare ``==`` would overwrite it with weights that were never found better)."""
+        ck, w, sp = self._checkpoint(), self.save_dir / "weights", int(self.args.save_period or 0)
+        torch.save(ck, w / "last.pt")
+        if self.best_fitness == self.fitness and self.best_epoch == self.epoch:
+            torch.save(ck, w / "best.pt")
+        if sp > 0 and self.epoch > 0 and self.epoch % sp == 0:
+            torch.save(ck, w / f"epoch{self.epoch}.pt")
+
+    def final_eval(self):
+        """reference engine/trainer.py:1038-1048: validate best.pt's EMA weights; ``self.metrics`` becomes that result.  Unlike the
+        reference, last.pt keeps its optimizer state (no strip_optimizer), so a finished run's last.pt stays resumable.  A run
+        without a save directory has no best.pt and keeps the last validation's metrics."""
+        best = None if self.save_dir is None else self.save_dir / "weights" / "best.pt"
+        if best is None or not best.exists() or self.validator is None:
+            return
+        LOGGER.info(f"Validating {best}...")
+        ck = torch.load(best, map_location="cpu", weights_only=False)
+        m = self.ema.eval_model()
+        m.load_state_dict(ck["ema"], strict=True)  # in place, into the flat buffers the evaluation model's parameters view
+        m._runtime(self.device).mark_dirty()
+        self.metrics = dict(self.validator(trainer=self, model=m))  # plain validation (args.plots as given); never TTA inside training
+        self.metrics.pop("fitness", None)
 
     def _check_replicas(self):
         """Data-parallel replicas must hold identical weights after every optimizer step (same start: setup()'s broadcast; same
@@ -357,6 +463,8 @@ class DetectionTrainer:
         p.ema_updates, self.last_opt_step = int(ck["updates"]), int(opt["last_opt_step"])
         p.opt_calls = int(f["state"][5]) + int(f["state"][6])
         rt.mark_dirty()
+        if ck.get("best_fitness") is not None:
+            self.best_fitness = ck["best_fitness"]  # reference engine/trainer.py:1102
         LOGGER.info(f"Resuming training from {path} from epoch {int(ck['epoch']) + 2} to {self.args.epochs} total epochs")
         return int(ck["epoch"]) + 1
 
@@ -396,7 +504,13 @@ class DetectionTrainer:
         self.train_loader = loader
         # per-image label capacity of the recorded loss kernels: derived from the label table, never below what the user asked for
         self.args.nmax = max(int(getattr(self.args, "nmax", 0) or 0), self._label_capacity(loader) or 8)
+        period = int(getattr(self.args, "val_period", 0) or 0)
+        if period >= 1 and self.rank == 0:  # the reference's loop: validate between epochs (ranks other than 0 never validate)
+            vloader = self.get_dataloader(self.data["val"], batch_size * 2, 0, "val", self.data)
+            self.validator = DetectionValidator(dataloader=vloader, args=self.args)
         hist = self.train(loader, batch_size, imgsz, log_every=log_every)  # log_every=1: per-epoch MEAN loss items, as results.csv
+        if period >= 1:
+            return hist  # self.metrics: final_eval's validation of best.pt
         self.metrics = None
         if self.args.val and self.rank == 0:
             vloader = self.get_dataloader(self.data["val"], batch_size * 2, 0, "val", self.data)
@@ -410,15 +524,21 @@ class DetectionTrainer:
         if reference_format:
             from ..nn.tasks import save_reference_format
             return save_reference_format(path, self.model, ema=self.ema.ema, updates=self.plan.ema_updates, train_args=vars(self.args))
+        torch.save(self._checkpoint(), path)
+
+    def _checkpoint(self):
         p, rt = self.plan, self.plan.rt
         flat = {"p": rt.flat_p, "b": rt.flat_b, "ema": p.ema, "ema_b": p.ema_b, "mom": p.mom, "state": p.state}
         if p.adam_v is not None:
             flat["adam_v"] = p.adam_v
-        torch.save({"epoch": getattr(self, "epoch", -1),
+        extra = {}
+        if int(getattr(self.args, "val_period", 0) or 0) >= 1 and hasattr(self, "stopper"):  # the loop's bookkeeping (reference :902-912)
+            extra = {"best_fitness": self.best_fitness, "fitness": self.fitness, "train_metrics": {**self.metrics, "fitness": self.fitness}}
+        return {"epoch": getattr(self, "epoch", -1), **extra,
                     "model": {k: v.detach().cpu() for k, v in self.model.state_dict().items()},
                     "ema": {k: v.detach().cpu() for k, v in self.ema.state_dict().items()},
                     "updates": p.ema_updates, "train_args": vars(self.args), "yaml": self.model.yaml,
                     # what resume needs (reference engine/trainer.py:911 keeps optimizer.state_dict()): the flat optimizer buffers
                     "optimizer": {"mode": p.mode, "param_names": list(rt.param_names), "last_opt_step": self.last_opt_step,
                                   "flat": {k: v.detach().cpu().clone() for k, v in flat.items()},
-                                  **({"soap": p.soap_state()} if p.soap else {})}}, path)
+                                  **({"soap": p.soap_state()} if p.soap else {})}}

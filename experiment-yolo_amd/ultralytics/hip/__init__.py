@@ -180,6 +180,7 @@ SIGNATURES = {
     "dy_tal_assign": (i32, [vp, ip, ip, C.POINTER(f32), i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "dy_head_infer_supported": (i32, [i32, i32, i32, i32]),
     "dy_head_infer_levels": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "dy_head_infer_levels_logits": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "dy_decode_predictions": (i32, [vp, vp, ip, ip, C.POINTER(f32), i32, i32, i32, i32, vp, vp]),
     "dy_nms_candidates": (i32, [vp, i32, i32, i32, f32, i32, vp, i32, vp, vp, vp, vp, i32, vp]),
     "dy_nms_presort_workspace": (sz, [i32, i32]),

@@ -40,6 +40,16 @@ def broadcast_buffers(flat_buffers: torch.Tensor, src: int = 0):
     return flat_buffers
 
 
+def broadcast_flag(flag, src: int = 0) -> bool:
+    """Rank ``src``'s boolean for every rank (the trainer's stop flag after an epoch, reference engine/trainer.py:878-883: only rank 0
+    validates and decides, every rank must leave the loop in the same epoch)."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        box = [bool(flag) if dist.get_rank() == src else None]
+        dist.broadcast_object_list(box, src)
+        return bool(box[0])
+    return bool(flag)
+
+
 def shard_batch(batch: dict, rank: int, world_size: int) -> dict:
     """DistributedSampler-style contiguous split of a batch dict (img, batch_idx, cls, bboxes) by image index."""
     B = batch["img"].shape[0]

@@ -72,14 +72,15 @@ class InferPlan:
         for fn, args, name, _ in self.rec.ops[:self.head]:
             check(fn(*[ptr if (isinstance(v, int) and v == ip) else v for v in args], s), name)
 
-    def _finish(self):
-        """Detect's tail into a fresh tensor (or, for heads the fused kernel does not take, the decode of the logits the list wrote)."""
+    def _finish(self, logits=False):
+        """Detect's tail into a fresh tensor (or, for heads the fused kernel does not take, the decode of the logits the list wrote).
+        ``logits``: the tail also writes its fp32 logits into ``ho.box`` / ``ho.cls`` (dy_head_infer_levels_logits)."""
         if self.ho.infer is not None:
-            return self.ho.infer()
+            return self.ho.infer(logits=logits)
         from ..utils.ops import decode_predictions
         return decode_predictions(self.ho)
 
-    def __call__(self, x):
+    def __call__(self, x, logits=False):
         if tuple(x.shape) != self.shape:
             raise ValueError(f"this plan was recorded for inputs of shape {self.shape}, got {tuple(x.shape)}")
         direct = self.rec is not None and self.head and x.dtype == torch.float32 and x.is_contiguous() and x.device == self.img.device
@@ -90,14 +91,14 @@ class InferPlan:
         self.calls += 1
         if self.rec is None:
             self._trace()
-            return self._finish()
+            return self._finish(logits)
         if self.head:
             self._head(x.data_ptr() if direct else self.img.data_ptr())
         if self.graph is not None:
             self.graph.replay()
         else:
             self.eng.replay(self.rec, self.head, None)
-        return self._finish()
+        return self._finish(logits)
 
 
 def wants_plan(model, x):
@@ -107,19 +108,21 @@ def wants_plan(model, x):
             and x.is_floating_point() and isinstance(model.model[-1], Detect))
 
 
-def forward_eval(model, x):
+def forward_eval(model, x, logits=False):
     """``model(x)`` in eval mode -> (y (B, 4+nc, A) fp32, LazyFeats): the recorded plan of this geometry when there is one, otherwise
-    the same launches issued by walking the modules (stem from the image batch, fused Detect tail): bit-identical results either way."""
+    the same launches issued by walking the modules (stem from the image batch, fused Detect tail): bit-identical results either way.
+    ``logits=True`` (a validation inside training, which computes the loss from the same forward): the Detect tail writes the fp32
+    logits behind the LazyFeats in the same launch instead of leaving them to ``materialize()``."""
     from ..nn.modules.head import LazyFeats
     plan = plan_for(model, x)
     with torch.no_grad():
         if plan is not None:
-            return plan(x), LazyFeats(plan.ho)
-        y, ho = walk_eval(model, x)
+            return plan(x, logits), LazyFeats(plan.ho)
+        y, ho = walk_eval(model, x, logits)
         return y, LazyFeats(ho)
 
 
-def walk_eval(model, x):
+def walk_eval(model, x, logits=False):
     """The eval forward's launches issued by walking the modules (no plan) -> (y, HeadOut)."""
     rt = model._runtime(x.device)
     eng = rt.eng
@@ -131,7 +134,7 @@ def walk_eval(model, x):
     finally:
         eng.infer_head = False
     if ho.infer is not None:
-        return ho.infer(), ho
+        return ho.infer(logits=logits), ho
     from ..utils.ops import decode_predictions
     return decode_predictions(ho), ho
 

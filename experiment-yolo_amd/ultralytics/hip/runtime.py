@@ -107,6 +107,8 @@ class Runtime:
             mod._buffers[bname] = view
             o += _round(k)
         self.n_buffers_flat = max(tot, PAD)
+        names = {id(mod): mname for mname, mod in self.root.named_modules()}
+        self.buffer_layout = [(f"{names[id(mod)]}.{bname}" if names[id(mod)] else bname, b.numel()) for mod, bname, b in fb]
         # integer buffers just move
         for mod in self.root.modules():
             for bname, b in list(mod._buffers.items()):
@@ -114,6 +116,11 @@ class Runtime:
                     mod._buffers[bname] = b.to(dev)
             if isinstance(mod, HipModule):
                 mod.__dict__["rt"] = self
+
+    def layout(self):
+        """Where every parameter and float buffer lives in the flat buffers: two runtimes with equal layouts can exchange ``flat_p`` /
+        ``flat_b`` wholesale (ModelEMA.eval_model)."""
+        return [(n, self.param_off[n]) for n in self.param_names], self.n_params_flat, self.buffer_layout, self.n_buffers_flat
 
     def refresh_frozen(self):
         """Re-read ``requires_grad`` flags (BaseTrainer freezes '.dfl' and the ``freeze=`` layers after construction, engine/trainer.py:

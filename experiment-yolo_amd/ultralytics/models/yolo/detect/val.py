@@ -28,6 +28,8 @@ class DetectionValidator:
         self.confusion_matrix = None
         self.stats = dict(tp=[], conf=[], pred_cls=[], target_cls=[])
         self.training = False
+        self.loss = None        # training mode: sum of the per-batch loss items (box, cls, dfl)
+        self.plots_gate = None  # training mode: the reference's ``args.plots &= possible_stop or final epoch`` (validator.py:118), args untouched
 
     # ---- reference validator hooks -------------------------------------------------------------------------------
     def init_metrics(self, model):
@@ -86,7 +88,8 @@ class DetectionValidator:
         tp = torch.zeros((ntot, self.niou), dtype=torch.uint8, device=dev)
         predn = dev_empty((ntot, 6), torch.float32, dev)
         ntgt = tcls.numel()
-        confusion = bool(self.args.plots and self.nc >= 1 and (ntot or ntgt))  # reference val.py:136; nothing to count in an empty batch
+        plots = self.args.plots if self.plots_gate is None else self.plots_gate
+        confusion = bool(plots and self.nc >= 1 and (ntot or ntgt))  # reference val.py:136; nothing to count in an empty batch
         if ntot or confusion:
             geom = torch.from_numpy(self._geometry(batch, B, imgsz)).to(dev)
             offd = torch.from_numpy(off).to(dev)
@@ -133,16 +136,37 @@ class DetectionValidator:
     # ---- driver (reference engine/validator.py:104-216, inference part) -------------------------------------------
     @torch.no_grad()
     def __call__(self, trainer=None, model=None):
+        """``validator(model=m)`` / ``validator(trainer=t, model=m)``: one validation of ``m`` (never TTA with a trainer).
+        ``validator(trainer=t)``: the reference's training mode (engine/validator.py:108-118, 180-181, 199-201) -- the trainer's
+        persistent EMA evaluation model, the validation loss summed per batch from the forward's own logits, the confusion matrix only on
+        the final epoch or when early stopping may strike; returns metrics + ``val/*_loss`` rounded to 5 decimals."""
         from ....utils.torch_utils import select_device
-        model = model if model is not None else trainer.model
-        self.device = next(model.parameters()).device if next(model.parameters()).is_cuda else select_device("0")
-        model.to(self.device).eval()
+        self.training = trainer is not None and model is None
+        if self.training:
+            model = trainer.ema.eval_model()
+            self.device = trainer.device
+            self.loss = torch.zeros(3, dtype=torch.float32, device=self.device)
+            self.plots_gate = bool(self.args.plots) and bool(trainer.stopper.possible_stop or trainer.epoch == trainer.args.epochs - 1)
+            model.eval()
+        else:
+            self.plots_gate = None
+            self.device = next(model.parameters()).device if next(model.parameters()).is_cuda else select_device("0")
+            if next(model.parameters()).device != self.device:  # (.to() on a model already there would only drop its runtime and plans)
+                model.to(self.device)
+            model.eval()
         self.init_metrics(model)
         augment = bool(self.args.augment) and trainer is None  # engine/validator.py:109: never while training
         for batch in self.dataloader:
             batch = self.preprocess(batch)
-            preds = self.postprocess(model(batch["img"], augment=augment))
-            self.update_metrics(preds, batch)
+            if self.training:
+                preds = model(batch["img"], logits=True)  # the Detect tail writes its fp32 logits beside y: model.loss has nothing to launch for them
+                self.loss += model.loss(batch, preds)[1]
+            else:
+                preds = model(batch["img"], augment=augment)
+            self.update_metrics(self.postprocess(preds), batch)
         stats = self.get_stats()
         self.print_results()
+        if self.training:
+            results = {**stats, **trainer.label_loss_items(self.loss.cpu() / len(self.dataloader), prefix="val")}
+            return {k: round(float(v), 5) for k, v in results.items()}
         return stats

@@ -14,6 +14,10 @@ from .conv import Conv
 
 __all__ = ("Detect",)
 
+# DY_HEAD_INFER_LOGITS=0: an eval forward asked for its logits (a validation inside training) issues the plain fused tail and leaves the
+# logits to ``HeadOut.materialize()`` (two eager final-conv launches per level) instead of dy_head_infer_levels_logits
+HEAD_INFER_LOGITS = os.environ.get("DY_HEAD_INFER_LOGITS", "1") != "0"
+
 
 class HeadOut:
     """Raw head outputs of one forward: per level fp32 (B,H,W,64) DFL logits and (B,H,W,ncp) class logits (ncp = nc
@@ -24,7 +28,8 @@ class HeadOut:
         self.dbox = self.dcls = None
         self.fill_box = None  # inside a StepPlan trace the box logits are not written (dy_head_box_decode); callable that writes them
         self.infer = None     # eval forward with the fused inference tail (Detect._infer_tail): callable -> y (B, 4+nc, A); box / cls
-                              # hold None until somebody asks for the logits (materialize)
+                              # hold None until somebody asks for the logits (materialize, or infer(logits=True) up front)
+        self.logits_current = False  # fused inference tail: box / cls hold the logits of the LAST forward (nothing to materialise)
 
     def materialize(self):
         """Write the box logits if the forward left them out (the recorded training step never reads them): an eager launch of the
@@ -117,20 +122,38 @@ class Detect(HipModule):
                 eng._arr(P, [sp.weight.data_ptr() for sp in csp]), eng._arr(P, [sp.bias.data_ptr() for sp in csp]),
                 eng._arr(I, [x.H for x in xs]), eng._arr(I, [x.W for x in xs]), eng._arr(F, ho.strides), B, csp[0].cin, self.nc)
 
-        def infer(y=None):
+        outs = []  # the logits launch's two pointer arrays, made with the buffers on first use
+
+        def alloc():
+            for l, x in enumerate(xs):
+                if ho.box[l] is None:
+                    ho.box[l] = torch.empty((x.N, x.H, x.W, nb), dtype=torch.float32, device=dev)
+                    ho.cls[l] = torch.zeros((x.N, x.H, x.W, ncp), dtype=torch.float32, device=dev)
+
+        def infer(y=None, logits=False):
+            """``logits=True``: the same launch also writes the fp32 logits into ``ho.box`` / ``ho.cls`` (a validation inside
+            training computes the loss from them), so a later ``materialize()`` launches nothing."""
             from ...hip import check
             if y is None:
                 y = torch.empty((B, 4 + self.nc, A), dtype=torch.float32, device=dev)
-            check(eng.L.dy_head_infer_levels(*args, y.data_ptr(), eng.stream), "dy_head_infer_levels")
+            if logits and HEAD_INFER_LOGITS:
+                if not outs:
+                    alloc()
+                    outs.extend((eng._arr(P, [t.data_ptr() for t in ho.box]), eng._arr(P, [t.data_ptr() for t in ho.cls])))
+                check(eng.L.dy_head_infer_levels_logits(*args, y.data_ptr(), *outs, eng.stream), "dy_head_infer_levels_logits")
+                ho.logits_current = True
+            else:
+                check(eng.L.dy_head_infer_levels(*args, y.data_ptr(), eng.stream), "dy_head_infer_levels")
+                ho.logits_current = False
             return y
 
         def fill():  # the logits themselves, for callers that index the per-level feature maps (reference head.py:74 returns them too)
             from ...hip import DY_EPI_BIAS, DY_EPI_F32OUT
             assert eng.rec is None, "logits can only be materialised outside a trace"
+            if ho.logits_current:
+                return
+            alloc()
             for l, x in enumerate(xs):
-                if ho.box[l] is None:
-                    ho.box[l] = torch.empty((x.N, x.H, x.W, nb), dtype=torch.float32, device=dev)
-                    ho.cls[l] = torch.zeros((x.N, x.H, x.W, ncp), dtype=torch.float32, device=dev)
                 eng._conv_raw(bsp[l], a[l], ho.box[l].data_ptr(), nb, DY_EPI_BIAS | DY_EPI_F32OUT, 0, bsp[l].bias)
                 eng._conv_raw(csp[l], c[l], ho.cls[l].data_ptr(), ncp, DY_EPI_BIAS | DY_EPI_F32OUT, 0, csp[l].bias)
         ho.infer, ho.fill_box = infer, fill

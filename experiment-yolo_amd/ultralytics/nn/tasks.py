@@ -145,10 +145,12 @@ class BaseModel(HipModule):
             return self.loss(x, *args, **kwargs)
         return self.predict(x, *args, **kwargs)
 
-    def predict(self, x, profile=False, visualize=False, augment=False, embed=None):
+    def predict(self, x, profile=False, visualize=False, augment=False, embed=None, logits=False):
         """Reference tasks.py:67-83.  In eval mode a detection model's forward of a (B, 3, H, W) device tensor goes through the
         inference plan of its geometry (hip/infer.py: recorded launch list / hipGraph, stem from the image batch, fused Detect tail).
-        ``augment=True``: test-time augmentation (reference tasks.py:335-371, hip/tta.py) -> (y, None), eval mode only."""
+        ``augment=True``: test-time augmentation (reference tasks.py:335-371, hip/tta.py) -> (y, None), eval mode only.
+        ``logits=True``: the eval forward's Detect tail also writes the fp32 logits behind the returned feature maps in its one launch
+        (what ``model.loss(batch, preds)`` reads); without it they are written on first access, as before."""
         if augment:
             from ..hip.tta import forward_tta, wants_tta
             if self.training:
@@ -159,7 +161,7 @@ class BaseModel(HipModule):
         if not self.training:
             from ..hip.infer import forward_eval, wants_plan
             if wants_plan(self, x):
-                return forward_eval(self, x)
+                return forward_eval(self, x, logits)
         return HipModule.forward(self, x)
 
     def _concat_plan(self):

@@ -48,6 +48,7 @@ class ModelEMA:
     def __init__(self, plan, decay=0.9999, tau=2000, updates=0):
         self.plan, self.decay0, self.tau = plan, decay, tau
         self.enabled = True
+        self._eval = None  # eval_model(): built once per run
 
     @property
     def updates(self):
@@ -85,3 +86,74 @@ class ModelEMA:
         m = DetectionModel(deepcopy(self.plan.model.yaml), verbose=False)
         m.load_state_dict({k: v.cpu() for k, v in self.state_dict().items()}, strict=True)
         return m.eval()
+
+    def eval_model(self):
+        """The run's ONE evaluation model, refreshed from the flat EMA buffers on the device (per-epoch validation,
+        reference engine/trainer.py:844-859 validates ``ema.ema``).  A model built from the same YAML flattens its parameters and
+        float buffers in the same order as the trained one (``Runtime._flatten``), so a refresh is two device copies and
+        ``mark_dirty()``: no host round trip, no ``load_state_dict``.  Its Runtime, packed-weight storage and recorded InferPlans
+        survive from epoch to epoch; only the packing pass reruns.  Carries ``names`` / ``nc`` / ``args`` / ``stride`` (reference
+        ``ema.update_attr``) and a criterion of its own (own result scalars and running WIoU mean; the box-loss modes are the
+        training criterion's), so a validation never touches the training criterion's state."""
+        plan, rt = self.plan, self.plan.rt
+        src = plan.model
+        m = self._eval
+        if m is None:
+            from ..nn.tasks import DetectionModel
+            dev = rt.eng.device
+            with torch.random.fork_rng(devices=[dev]):  # the constructor draws initial weights: the training run's RNG streams stay where they were
+                m = DetectionModel(deepcopy(src.yaml), verbose=False)
+            m.to(dev).eval()
+            ert = m._runtime(dev)
+            if ert.layout() != rt.layout():
+                raise RuntimeError("ModelEMA.eval_model: a model built from the plan's YAML does not lay its parameters and buffers out like "
+                                   "the trained one (was the trained model modified after construction?)")
+            if ert.flat_p.numel() != plan.ema.numel() or ert.flat_b.numel() != plan.ema_b.numel():
+                raise RuntimeError("ModelEMA.eval_model: flat buffer sizes differ from the EMA buffers'")
+            self._eval = m
+        ert = m._runtime(rt.eng.device)
+        ert.flat_p.copy_(plan.ema)
+        ert.flat_b.copy_(plan.ema_b)
+        for (_, b), (_, e) in zip(src.named_buffers(), m.named_buffers()):  # integer buffers (num_batches_tracked, ...) are copied
+            if not b.dtype.is_floating_point:
+                e.copy_(b)
+        ert.mark_dirty()
+        for k in ("names", "args"):
+            if hasattr(src, k):
+                setattr(m, k, getattr(src, k))
+        m.nc = getattr(src, "nc", src.model[-1].nc)
+        if "criterion" not in m.__dict__:
+            crit, bl = m.init_criterion(), plan.crit.bbox_loss
+            eb = crit.bbox_loss
+            eb.use_wiseiou, eb.nwd_loss, eb.iou_ratio = bl.use_wiseiou, bl.nwd_loss, bl.iou_ratio
+            eb.configure_from_cfg(getattr(src, "args", None))
+            for k in ("iou_type", "iou_variant", "inner_ratio", "focaler_d", "focaler_u", "shape_scale", "piou_lambda"):
+                setattr(eb, k, getattr(bl, k))
+            m.criterion = crit
+        return m.eval()
+
+
+class EarlyStopping:
+    """Stops a run when the fitness has not improved for ``patience`` epochs (semantics of reference utils/torch_utils.py:568-610):
+    an equal fitness counts as an improvement (``>=``: the early zero-fitness epochs move ``best_epoch`` along), ``possible_stop``
+    announces that the next epoch may stop, ``patience=0`` never stops, ``fitness=None`` (an epoch without a validation yet) changes
+    nothing."""
+
+    def __init__(self, patience=50):
+        self.best_fitness, self.best_epoch = 0.0, 0
+        self.patience = patience or float("inf")
+        self.possible_stop = False
+
+    def __call__(self, epoch, fitness):
+        if fitness is None:
+            return False
+        if fitness >= self.best_fitness:
+            self.best_epoch, self.best_fitness = epoch, fitness
+        since = epoch - self.best_epoch
+        self.possible_stop = since >= self.patience - 1
+        if since >= self.patience:
+            from . import LOGGER
+            LOGGER.info(f"Stopping training early: no improvement in the last {self.patience} epochs; best results at epoch "
+                        f"{self.best_epoch}, saved as best.pt (patience=0 disables early stopping)")
+            return True
+        return False

@@ -508,6 +508,14 @@ int dy_head_infer_supported(int cin_box, int cout_box, int cin_cls, int nc);
 int dy_head_infer_levels(int nl, const void* const* x_box, const int* ld_box, const float* const* w_box, const float* const* b_box,
                          const void* const* x_cls, const int* ld_cls, const float* const* w_cls, const float* const* b_cls, const int* h,
                          const int* w, const float* stride, int n, int cin_cls, int nc, float* y, hipStream_t stream);
+/* The same launch, which also writes the logits it computes on the way: per level box_logits[l] (B,H,W,64) and cls_logits[l]
+ * (B,H,W,ncp) fp32, ncp = nc rounded up to 8 with channels [nc, ncp) exact zeros; 16-byte aligned.  Bit for bit what dy_conv_forward
+ * (fp32 out + bias) writes over the same activations, and y bit for bit dy_head_infer_levels': a validation inside training hands the
+ * logits to the loss without re-reading the activations.  Same supported shapes and error codes. */
+int dy_head_infer_levels_logits(int nl, const void* const* x_box, const int* ld_box, const float* const* w_box, const float* const* b_box,
+                                const void* const* x_cls, const int* ld_cls, const float* const* w_cls, const float* const* b_cls,
+                                const int* h, const int* w, const float* stride, int n, int cin_cls, int nc, float* y,
+                                float* const* box_logits, float* const* cls_logits, hipStream_t stream);
 int dy_decode_predictions(const float* const* box, const float* const* cls, const int* H, const int* W,
                           const float* stride, int nl, int B, int nc, int ncp, float* y, hipStream_t stream);
 /* ---- ops.non_max_suppression utils/ops.py:292-427: candidate extraction (:344-392, order-preserving) ... */
