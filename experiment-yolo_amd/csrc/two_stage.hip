@@ -11,6 +11,7 @@
 #include "common.h"
 #include "dealyolo_hip.h"
 #pragma clang fp contract(off)
+#include "two_stage_iou.h"
 
 static inline int grid_for(long total) {
   long b = (total + 255) / 256;
@@ -70,17 +71,6 @@ extern "C" int dy_crop_letterbox_u8(const void* img, int H, int W, const int* re
   hipLaunchKernelGGL(crop_letterbox_kernel, dim3(grid_for((long)K * S * S)), dim3(256), 0, stream, a);
   DY_CHECK_LAUNCH();
   return DY_OK;
-}
-
-// IoU of calculate_iou_tensor (:70-87): 0 for empty intersection or a non-positive area, no epsilon.
-static __device__ __forceinline__ float iou_plain(float ax1, float ay1, float ax2, float ay2, float bx1, float by1, float bx2, float by2) {
-  const float x1 = fmaxf(ax1, bx1), y1 = fmaxf(ay1, by1), x2 = fminf(ax2, bx2), y2 = fminf(ay2, by2);
-  if (x2 <= x1 || y2 <= y1) return 0.f;
-  const float inter = (x2 - x1) * (y2 - y1);
-  const float a1 = (ax2 - ax1) * (ay2 - ay1), a2 = (bx2 - bx1) * (by2 - by1);
-  if (a1 <= 0.f || a2 <= 0.f) return 0.f;
-  const float uni = a1 + a2 - inter;
-  return uni > 0.f ? inter / uni : 0.f;
 }
 
 struct RefineArgs {

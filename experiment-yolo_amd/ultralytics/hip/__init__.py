@@ -124,6 +124,9 @@ SIGNATURES = {
     "dy_crop_letterbox_u8": (i32, [vp, i32, i32, vp, vp, i32, i32, vp, vp]),
     "dy_refine_select": (i32, [vp, vp, vp, vp, vp, i32, C.c_float, C.c_float, vp, vp, vp]),
     "dy_nms_hard": (i32, [vp, vp, vp, i32, C.c_float, vp, vp]),
+    "dy_crop_letterbox_u8_multi": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "dy_refine_select_multi": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
+    "dy_two_stage_merge": (i32, [vp, vp, vp, vp, vp, vp, i32, f32, vp, vp, f32, i32, vp, vp, vp, vp]),
     "dy_warp_import_u8": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "dy_warp_slot_bytes": (i32, []),
     "dy_import_image_u8": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),

@@ -577,6 +577,32 @@ int dy_refine_select(const float* dets, const int* offsets, const float* orig, c
 int dy_nms_hard(const float* boxes, const float* scores, const float* labels, int n, float iou_thr, void* keep,
                 hipStream_t stream);
 
+/* ---- two-stage inference over a chunk of N images, double_inference.py main :509-562 (process_image_optimized :404-449 per image,
+ *      calculate_metrics_optimized :306-333 for the counts): the three kernels above for many images per launch.
+ * dy_crop_letterbox_u8 for K crops of N images of different sizes in one launch (the per-image open / crop / resize / pad of
+ * perform_batch_double_inference :206-226).  pool: the uint8 HWC images back to back; img_off (N) int64 byte offsets, any alignment;
+ * img_hw (N,2) height, width; crop_img (K) the image of each crop; rects / geom / out as dy_crop_letterbox_u8.  Every crop holds the
+ * bits dy_crop_letterbox_u8 writes for its image alone.  The caller guarantees 0 <= crop_img[k] < N and rects inside their image. */
+int dy_crop_letterbox_u8_multi(const void* pool, const long* img_off, const int* img_hw, const int* crop_img, const int* rects,
+                               const int* geom, int K, int S, void* out, hipStream_t stream);
+/* dy_refine_select with the bounds filter of process_refined_boxes_optimized (:277-280: x2 <= img_w, y2 <= img_h) taken from the
+ * crop's own image: crop_img (K), img_hw (N,2) height, width. */
+int dy_refine_select_multi(const float* dets, const int* offsets, const float* orig, const int* rects, const float* scale,
+                           const int* crop_img, const int* img_hw, int K, float* out, int* found, hipStream_t stream);
+/* The rest of process_image_optimized (:430-444) and calculate_metrics_optimized (:306-333) for N images in one launch, one workgroup
+ * per image.  rows (M,6) x1 y1 x2 y2 conf cls: the first-stage detections of the chunk with row_off (N+1), in/out; refined (K,6) and
+ * found (K) from dy_refine_select_multi with crop_off (N+1); crop_row (K) indexes rows and ascends within an image; labels (L,5) fp32
+ * cls x1 y1 x2 y2 in native pixels (load_ground_truth :492-506) with lab_off (N+1).
+ *  1. apply: aligned != 0, a found refinement k replaces rows[crop_row[k]]; aligned == 0, the script's zip (:431): the j-th FOUND
+ *     refinement of an image replaces rows[crop_row[crop_off[b] + j]].
+ *  2. dy_nms_hard on the image's rows after step 1 -> keep (M) bytes.  nms_iou < 0 skips the sweep (every row kept).
+ *  3. the kept rows in stored order each take, among the unmatched labels of their class, the one of largest IoU (calculate_iou_tensor,
+ *     fp32) if it is >= match_iou and > 0; ties to the first label.  counts (N,3) int32 = tp, fp, fn.
+ * *status |= 1 and nothing is written for an image with more than 2048 rows or 1024 labels. */
+int dy_two_stage_merge(float* rows, const int* row_off, const float* refined, const int* found, const int* crop_row,
+                       const int* crop_off, int aligned, float nms_iou, const float* labels, const int* lab_off, float match_iou,
+                       int N, void* keep, int* counts, int* status, hipStream_t stream);
+
 /* ---- test-time augmentation, reference nn/tasks.py:335-371 (DetectionModel._predict_augment / _descale_pred / _clip_augmented) and
  *      utils/torch_utils.py:355-366 (scale_img); the pass geometry is host arithmetic (ultralytics/hip/tta.py).
  * scale_img of one pass in one launch: x (B, 3, H, W) fp32 NCHW -> out (B, 3, Hp, Wp) fp32 NCHW = x flipped (flip 0: none,
