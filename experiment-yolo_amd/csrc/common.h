@@ -15,6 +15,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define DY_ERR_ARG (-1)      // unsupported shape / bad argument
 #define DY_ERR_LAUNCH (-2)   // hipGetLastError() != success after launch
 #define DY_ERR_ALIGN (-3)    // pointer / stride alignment the kernel relies on is violated
+#define DY_ERR_CAPACITY (-4) // more items than a kernel's fixed table holds
 
 #define LDS_AS __attribute__((address_space(3)))
 

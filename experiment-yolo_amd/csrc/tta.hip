@@ -99,12 +99,7 @@ struct MergeArgs {
   float H, W;
 };
 
-static __device__ __forceinline__ float div_rn(float x, float s, float rs) {
-#pragma clang fp contract(off)
-  const float q = x * rs;
-  const float q1 = __builtin_fmaf(__builtin_fmaf(-q, s, x), rs, q);
-  return __builtin_fmaf(__builtin_fmaf(-q1, s, x), rs, q1);
-}
+#include "div_rn.h"
 
 #define DY_MERGE_PER_THREAD 4
 __global__ __launch_bounds__(256) void tta_merge_kernel(MergeArgs a) {

@@ -10,6 +10,7 @@
 #include "dealyolo_hip.h"
 #pragma clang fp contract(off)
 #include "two_stage_iou.h"
+#include "crop_pixel.h"
 
 struct CropMultiArgs {
   const unsigned char* pool;  // uint8 HWC images back to back
@@ -21,34 +22,6 @@ struct CropMultiArgs {
   unsigned char* out;         // (K, S, S, 3)
   int K, S;
 };
-
-// One output pixel: the expressions of crop_letterbox_kernel (two_stage.hip), in its order.
-static __device__ __forceinline__ void crop_pixel(const unsigned char* img, int W, int x1, int y1, int cw, int ch, int nw, int nh, int px,
-                                                  int py, int ox, int oy, unsigned char* v) {
-  v[0] = 114; v[1] = 114; v[2] = 114;
-  const int dx = ox - px, dy = oy - py;
-  if (dx >= 0 && dx < nw && dy >= 0 && dy < nh && cw > 0 && ch > 0) {
-    float fx = ((float)dx + 0.5f) * ((float)cw / (float)nw) - 0.5f;
-    float fy = ((float)dy + 0.5f) * ((float)ch / (float)nh) - 0.5f;
-    int sx = (int)floorf(fx), sy = (int)floorf(fy);
-    fx -= (float)sx;
-    fy -= (float)sy;
-    if (sx < 0) { sx = 0; fx = 0.f; }
-    if (sx >= cw - 1) { sx = cw - 1; fx = 0.f; }
-    if (sy < 0) { sy = 0; fy = 0.f; }
-    if (sy >= ch - 1) { sy = ch - 1; fy = 0.f; }
-    const int sx1 = min(sx + 1, cw - 1), sy1 = min(sy + 1, ch - 1);
-    const unsigned char* p00 = img + ((long)(y1 + sy) * W + x1 + sx) * 3;
-    const unsigned char* p01 = img + ((long)(y1 + sy) * W + x1 + sx1) * 3;
-    const unsigned char* p10 = img + ((long)(y1 + sy1) * W + x1 + sx) * 3;
-    const unsigned char* p11 = img + ((long)(y1 + sy1) * W + x1 + sx1) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float top = (float)p00[c] * (1.f - fx) + (float)p01[c] * fx, bot = (float)p10[c] * (1.f - fx) + (float)p11[c] * fx;
-      v[c] = (unsigned char)fminf(fmaxf(rintf(top * (1.f - fy) + bot * fy), 0.f), 255.f);
-    }
-  }
-}
 
 struct __attribute__((aligned(4))) Px4 { unsigned int w[3]; };  // four RGB pixels = three dwords
 
@@ -81,13 +54,6 @@ __global__ __launch_bounds__(256) void crop_letterbox_multi_kernel(CropMultiArgs
       o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
     }
   }
-}
-
-static inline int grid_for(long total) {
-  long b = (total + 255) / 256;
-  if (b > 16384) b = 16384;
-  if (b < 1) b = 1;
-  return (int)b;
 }
 
 extern "C" int dy_crop_letterbox_u8_multi(const void* pool, const long* img_off, const int* img_hw, const int* crop_img, const int* rects,

@@ -16,11 +16,11 @@ for _k, _v in DEFAULT_CFG_DICT.items():
 CFG_FLOAT_KEYS = "warmup_epochs", "box", "cls", "dfl", "degrees", "shear", "time", "loss_scale"
 CFG_FRACTION_KEYS = ("dropout", "iou", "lr0", "lrf", "momentum", "weight_decay", "warmup_momentum", "warmup_bias_lr",
                      "label_smoothing", "hsv_h", "hsv_s", "hsv_v", "translate", "scale", "perspective", "flipud", "fliplr",
-                     "mosaic", "mixup", "copy_paste", "conf", "fraction", "iou_ratio")
+                     "mosaic", "mixup", "copy_paste", "conf", "fraction", "iou_ratio", "tile_overlap", "tile_iou")
 CFG_INT_KEYS = ("epochs", "patience", "batch", "workers", "seed", "close_mosaic", "max_det", "vid_stride", "nbs", "save_period", "mask_ratio",
-                "nmax", "val_period")
+                "nmax", "val_period", "tile")
 CFG_BOOL_KEYS = ("save", "exist_ok", "verbose", "deterministic", "single_cls", "rect", "cos_lr", "amp", "val", "half",
-                 "agnostic_nms", "plots", "wiou", "nwd", "hipgraph", "multi_scale", "overlap_mask", "wiou_inner", "wiou_focaler")
+                 "agnostic_nms", "plots", "wiou", "nwd", "hipgraph", "multi_scale", "overlap_mask", "wiou_inner", "wiou_focaler", "tile_full")
 
 
 class IterableSimpleNamespace(SimpleNamespace):

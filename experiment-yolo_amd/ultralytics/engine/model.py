@@ -146,7 +146,7 @@ class YOLO:
         """reference engine/model.py:386-440 ``model.predict(source=..., imgsz=..., conf=..., ...)`` -> list of ``Results``.
         ``source``: image file | directory | glob | list | PIL | BGR ndarray | (B,3,H,W) tensor in [0,1]."""
         from .predictor import DetectionPredictor
-        args = {**self.overrides, "conf": 0.25, "batch": 1, **kwargs, "mode": "predict"}
+        args = {"tile": None, **self.overrides, "conf": 0.25, "batch": 1, **kwargs, "mode": "predict"}  # tile: off unless this call asks
         verbose = args.pop("verbose", False)  # the reference's default is True (it logs every image)
         if self.predictor is None or predictor is not None:
             self.predictor = (predictor or DetectionPredictor)(overrides=dict(args, verbose=verbose))

@@ -140,6 +140,8 @@ class DetectionPredictor:
             raise ValueError("predict needs a source (image file, directory, glob, list, PIL image, BGR ndarray or BCHW tensor)")
         paths, data = load_source(source)
         n = len(paths)
+        if self.args.tile is not None:
+            return self._call_tiled(paths, data)
         bs = n if isinstance(data, torch.Tensor) else max(1, int(self.args.batch or 1))
         results = []
         for lo in range(0, n, bs):
@@ -160,6 +162,23 @@ class DetectionPredictor:
             results += res
         if self.args.save_txt or self.args.save_crop or self.args.save_conf:
             LOGGER.warning("WARNING save_txt / save_crop / save_conf: writing results is control plane, not provided by this package")
+        self.results = results
+        return results
+
+    def _call_tiled(self, paths, imgs):
+        """``tile=`` set: sliced inference (utils/tiled.py) on the native images; ``batch`` = tiles per forward."""
+        from ..utils.tiled import tiled_predict
+        a = self.args
+        if isinstance(imgs, torch.Tensor):
+            raise ValueError("tile= needs image sources (files, PIL images, ndarrays): tiles are cut from images, not from letterboxed batches")
+        t0 = time.perf_counter()
+        boxes = tiled_predict(imgs, self.model, tile=a.tile, overlap=a.tile_overlap, conf=a.conf, iou=a.iou, merge_iou=a.tile_iou,
+                              metric=a.tile_metric, full_image=a.tile_full, batch=max(1, int(a.batch or 1)), agnostic=a.agnostic_nms,
+                              classes=a.classes, max_det=a.max_det, augment=bool(a.augment))
+        ms = (time.perf_counter() - t0) * 1e3 / max(1, len(imgs))
+        results = [Results(orig, path=p, names=self.model.names, boxes=b) for orig, p, b in zip(imgs, paths, boxes)]
+        for r in results:
+            r.speed = {"preprocess": 0.0, "inference": ms, "postprocess": 0.0}
         self.results = results
         return results
 

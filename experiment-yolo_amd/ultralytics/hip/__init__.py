@@ -38,7 +38,7 @@ DY_EPI_STATS, DY_EPI_BIAS, DY_EPI_SILU, DY_EPI_F32OUT, DY_EPI_ACCUM, DY_EPI_STAT
 DY_BN_COPIES = 16  # include/dealyolo_hip.h
 DY_ACT_NONE, DY_ACT_SILU, DY_ACT_LEAKY = 0, 1, 2
 _ERR = {-1: "DY_ERR_ARG (unsupported shape/argument)", -2: "DY_ERR_LAUNCH (HIP launch failed)",
-        -3: "DY_ERR_ALIGN (pointer/stride alignment)"}
+        -3: "DY_ERR_ALIGN (pointer/stride alignment)", -4: "DY_ERR_CAPACITY (more items than the kernel's table holds)"}
 
 vp, i32, f32, i64, sz = C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_size_t
 ip = C.POINTER(C.c_int)
@@ -127,6 +127,8 @@ SIGNATURES = {
     "dy_crop_letterbox_u8_multi": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
     "dy_refine_select_multi": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]),
     "dy_two_stage_merge": (i32, [vp, vp, vp, vp, vp, vp, i32, f32, vp, vp, f32, i32, vp, vp, vp, vp]),
+    "dy_tile_gather_f32": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp]),
+    "dy_tile_merge": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp, vp]),
     "dy_warp_import_u8": (i32, [vp, vp, vp, i32, i32, i32, vp]),
     "dy_warp_slot_bytes": (i32, []),
     "dy_import_image_u8": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),

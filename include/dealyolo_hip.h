@@ -31,6 +31,7 @@ typedef struct ihipStream_t* hipStream_t;
 #define DY_ERR_ARG (-1)
 #define DY_ERR_LAUNCH (-2)
 #define DY_ERR_ALIGN (-3)
+#define DY_ERR_CAPACITY (-4) /* more items than a kernel's fixed table holds; nothing was launched */
 
 /* A channel CONCATENATION that is never materialised: the tensor's channels [c_end[s-1], c_end[s]) live in segment s, an fp16 NHWC
  * tensor (or channel slice) of its own pixel stride.  C2f's ``torch.cat(y, 1)`` (nn/modules/block.py:222-226), SPPF's and the model's
@@ -652,6 +653,35 @@ int dy_confusion_matrix(const float* predn, const int* pred_off, int n_preds, co
  *      arithmetic on the fp32 detections: equal away from the threshold.  *status |= 1 if an image has > 1024 labels. */
 int dy_count_fp(const float* dets, const int* det_off, const double* labels, const int* lab_off, const int* wh, int B, float conf_thr,
                 double iou_thr, int* fp, int* status, hipStream_t stream);
+
+/* ---- sliced (tiled) inference for frames much larger than the model input (ultralytics/utils/tiled.py): the frame is cut into
+ *      overlapping S x S tiles, optionally plus one letterboxed view of the whole frame; every record goes through the model at S x S
+ *      and the detections of all records are merged per frame.
+ * dy_tile_gather_f32: K records of N images into out (K,3,S,S) fp32 planar -- the input tensor of the forward itself.  pool / img_off /
+ * img_hw / rects / geom as dy_crop_letterbox_u8_multi; tile_img (K) the image of each record, < 0 = a pad canvas (all 114; its rect and
+ * geom are not read).  Every value is lut[u] with u the byte dy_crop_letterbox_u8_multi writes for that pixel and channel; lut (256)
+ * device floats, the caller's byte -> float conversion (u / 255 as the caller's framework rounds it).  A thread writes four pixels of a
+ * row per plane as one 16-byte store when S % 4 == 0 and out is 16-byte aligned, single floats otherwise.  The caller guarantees
+ * tile_img[k] < N and rects inside their image. */
+int dy_tile_gather_f32(const void* pool, const long* img_off, const int* img_hw, const int* tile_img, const int* rects, const int* geom,
+                       const float* lut, int K, int S, float* out, hipStream_t stream);
+/* dy_tile_merge: N images in one launch, one workgroup per image.  rows (M,6) x1 y1 x2 y2 score label in the coordinates of their
+ * record's canvas, packed image-major with row_off (N+1); row_tile (M) indexes tiles (Kt,6) = x1, y1, pad_x, pad_y, r, 1/r of the
+ * record (fp32; 1/r the correctly rounded reciprocal); img_hw (N,2) height, width.
+ *  1. out (M,6): every coordinate v -> (v - pad) / r + origin in fp32, each operation rounded once (the quotient is the correctly
+ *     rounded one; r == 1 gives v + origin exactly), x clipped to [0, W], y to [0, H].  A row whose clipped width or height is <= 0 (or
+ *     whose score is NaN) is written but takes no further part.
+ *  2. per image the remaining rows in descending score, ties to the lower row index; walking that order, a surviving row is kept and
+ *     removes every later surviving row of the same label (any label when agnostic) whose metric with it is > thr.  metric 0: IoU
+ *     (0 for an empty intersection or a non-positive area, no epsilon); 1: the same intersection over the smaller of the two areas.
+ *  order (M): the kept row indices (into rows) of image i in that order from order[row_off[i]]; nkeep (N) their number.
+ * max_rows: the largest row count of an image (the host knows it; row_off is device memory): above DY_TILE_MERGE_MAX_ROWS the call
+ * returns DY_ERR_CAPACITY and launches nothing -- never a truncated result.  *status |= 1 if an image nevertheless exceeds the
+ * capacity (it gets nkeep 0), |= 2 if a row_tile lies outside [0, Kt) (that row is copied through and dropped). */
+#define DY_TILE_MERGE_MAX_ROWS 8192
+int dy_tile_merge(const float* rows, const int* row_off, const int* row_tile, const float* tiles, const int* img_hw, int N, int Kt,
+                  int max_rows, float thr, int metric, int agnostic, float* out, int* order, int* nkeep, int* status,
+                  hipStream_t stream);
 
 #ifdef __cplusplus
 }
