@@ -695,7 +695,7 @@ __global__ __launch_bounds__(256) void scalseq_tail_kernel(SsArgs a) {
       for (int j = 0; j < 8; ++j) {
         float z = (float)v[j] * a.coef[c0 + j] + a.coef[a.C + c0 + j];
         z = z > 0.f ? z : 0.1f * z;
-        best[j] = (l == 0) ? z : fmaxf(best[j], z);
+        if (l == 0 || z > best[j] || z != z) best[j] = z;  // a NaN replaces the running maximum and stays: max_pool3d propagates it
       }
     }
     half8 o;

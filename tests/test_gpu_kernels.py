@@ -372,7 +372,9 @@ def test_wgrad_deferred_batched_reduce_matches_immediate():
 @pytest.mark.parametrize("H,W,Cc", [(16, 24, 16), (16, 32, 32), (8, 64, 16), (12, 16, 64)])
 def test_scalseq_backward_all_levels_matches_per_level(H, W, Cc):
     """dy_scalseq_tail_backward_all (one pass per mode) against the per-level entry point it replaced in the engine.  (16, 24, 16) takes
-    the block-per-lane kernel (24 columns are no multiple of 32), the other shapes the column-per-lane one."""
+    the block-per-lane kernel (24 columns are no multiple of 32), the other shapes the column-per-lane one.  The engine calls only the
+    all-levels entry point now, so this is a consistency check between two kernels; both are compared with the float64 closed form (itself
+    tied to autograd through the reference module's tail) in tests/test_gpu_tensor_ops.py, section 2."""
     import ctypes as C
     eng = _eng()
     L = eng.L
