@@ -13,6 +13,12 @@ static inline int grid_for(long total) {
   if (b < 1) b = 1;
   return (int)b;
 }
+// DY_TENSOR_OPS_V1=1 (read at every call): dy_scalseq_tail_backward_all and dy_sppf_pool3 launch the kernels they launched before
+// scalseq_bwd_v2_kernel and sppf_pool3_fwd_v2_kernel existed (A/B runs, bit tests); dy_sppf_pool3_backward has one kernel
+static bool tensor_ops_v1() {
+  const char* e = getenv("DY_TENSOR_OPS_V1");
+  return e && e[0] == '1' && !e[1];
+}
 
 // ---- NCHW fp32 image -> NHWC fp16 with channels zero-padded to Cp (stem input)
 __global__ __launch_bounds__(256) void import_image_kernel(const float* x, f16* y, int N, int C, int H, int W, int Cp,
@@ -467,9 +473,8 @@ struct SppfArgs {
   int ld, C, N, H, W, acc[3];
 };
 template <int CG>
-__global__ __launch_bounds__(SPPF_THREADS) void sppf_pool3_fwd_kernel(SppfArgs a) {
+static __device__ __forceinline__ void sppf_pool3_fwd_body(const SppfArgs& a, char* sppf_lds) {
   constexpr int G = CG / 8;
-  extern __shared__ __attribute__((aligned(16))) char sppf_lds[];
   const int HW = a.H * a.W, items = HW * G;
   half8* cur = reinterpret_cast<half8*>(sppf_lds);          // the map being pooled; overwritten by its pooled form
   half8* rowm = cur + items;                                 // row-pass maxima
@@ -534,6 +539,116 @@ __global__ __launch_bounds__(SPPF_THREADS) void sppf_pool3_fwd_kernel(SppfArgs a
       cur[i] = o;  // only this thread reads or writes cur[i] in this pass: the column pass reads the row results
       *reinterpret_cast<half8*>(yb + (size_t)px * a.ld + part * 8) = o;
       if (ab) *reinterpret_cast<uint2*>(ab + (size_t)px * a.C + part * 8) = *reinterpret_cast<const uint2*>(bi);
+    }
+    __syncthreads();
+  }
+}
+template <int CG>
+__global__ __launch_bounds__(SPPF_THREADS) void sppf_pool3_fwd_kernel(SppfArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char sppf_lds[];
+  sppf_pool3_fwd_body<CG>(a, sppf_lds);
+}
+// The same three pools on integer keys.  The passes above spend six vector instructions per tap and channel (convert, two compares, or,
+// two selects) and are bound by them.  Here a granule is staged as order-preserving 16-bit keys (key = h | 0x8000 for h >= 0, ~h for
+// h < 0), a tap becomes one 32-bit word (key << 16 | preference) and the running "first maximum" one unsigned max per channel (two taps per
+// v_max3_u32).  The preference is ABSOLUTE, 63 - column in the row pass and (63 - row) * 5 + (4 - dx) in the column pass: the smallest
+// column / row wins a tie whatever window looks at it, and a tap clamped to the border only repeats a word the window already holds, so the
+// border needs no branch.  The winner's low half gives the window code by one subtraction, its high half the value (the key inverted).
+// An all -inf window keeps code 0, as above (nothing is ever greater than the initial -inf).
+// Keys cannot carry a NaN's "last one wins" or the sign of a zero that ties with the other zero: a workgroup whose tile holds a NaN or a
+// -0 takes the passes above instead (y1..y3 only repeat values of x, so the test is made once, on x).  H, W <= 63.
+template <int CG>
+__global__ __launch_bounds__(SPPF_THREADS) void sppf_pool3_fwd_v2_kernel(SppfArgs a) {
+  constexpr int G = CG / 8;
+  constexpr unsigned KNINF = 0x03ffu;  // key of -inf
+  extern __shared__ __attribute__((aligned(16))) char sppf_lds[];
+  const int HW = a.H * a.W, items = HW * G;
+  uint4* cur = reinterpret_cast<uint4*>(sppf_lds);   // keys of the map being pooled, 8 per granule
+  uint4* row0 = cur + items;                         // row-pass words of channels 0..3
+  uint4* row1 = row0 + items;                        //                            4..7
+  int* special = reinterpret_cast<int*>(row1 + items);
+  const int groups = a.C / CG, n = blockIdx.x / groups, c0 = (blockIdx.x - n * groups) * CG;
+  f16* const base = a.cat + (size_t)n * HW * a.ld + c0;
+  if (threadIdx.x == 0) *special = 0;
+  __syncthreads();
+  bool bad = false;
+  for (int i = threadIdx.x; i < items; i += SPPF_THREADS) {
+    const int px = i / G, part = i - px * G;
+    const uint4 v = *reinterpret_cast<const uint4*>(base + (size_t)px * a.ld + part * 8);
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+    unsigned k[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      const unsigned lo = w[d] & 0xffffu, hi = w[d] >> 16;
+      bad |= (lo & 0x7fffu) > 0x7c00u || lo == 0x8000u || (hi & 0x7fffu) > 0x7c00u || hi == 0x8000u;
+      k[d] = w[d] ^ ((((w[d] >> 15) & 0x00010001u) * 0xffffu) | 0x80008000u);
+    }
+    cur[i] = uint4{k[0], k[1], k[2], k[3]};
+  }
+  if (bad) *special = 1;
+  __syncthreads();
+  if (*special) {  // the same answer for every thread of the workgroup
+    __syncthreads();
+    sppf_pool3_fwd_body<CG>(a, sppf_lds);
+    return;
+  }
+  for (int l = 0; l < 3; ++l) {
+    for (int i = threadIdx.x; i < items; i += SPPF_THREADS) {
+      const int px = i / G, part = i - px * G, y = px / a.W, x = px - y * a.W;
+      unsigned best[8];
+#pragma unroll
+      for (int dx = 0; dx < 5; ++dx) {
+        const int xx = min(max(x + dx - 2, 0), a.W - 1);
+        const unsigned t = (unsigned)(63 - xx);
+        const uint4 v = cur[(y * a.W + xx) * G + part];
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          const unsigned lo = (w[d] << 16) | t, hi = (w[d] & 0xffff0000u) | t;
+          best[2 * d] = dx ? max(best[2 * d], lo) : lo;
+          best[2 * d + 1] = dx ? max(best[2 * d + 1], hi) : hi;
+        }
+      }
+      // low half for the column pass: (63 - y) * 5 + (4 - dx), 4 - dx = (63 - xx) + (x - 61); an all -inf window keeps dx = 0
+      const int kx = (63 - y) * 5 + x - 61, ninf = (63 - y) * 5 + 4;
+      unsigned o[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const unsigned low = (best[j] >> 16) == KNINF ? (unsigned)ninf : (unsigned)((int)(best[j] & 0xffffu) + kx);
+        o[j] = (best[j] & 0xffff0000u) | low;
+      }
+      row0[i] = uint4{o[0], o[1], o[2], o[3]};
+      row1[i] = uint4{o[4], o[5], o[6], o[7]};
+    }
+    __syncthreads();
+    f16* const yb = base + (size_t)(l + 1) * a.C;
+    uint8_t* const ab = a.arg[l] ? a.arg[l] + (size_t)n * HW * a.C + c0 : nullptr;
+    for (int i = threadIdx.x; i < items; i += SPPF_THREADS) {
+      const int px = i / G, part = i - px * G, y = px / a.W, x = px - y * a.W;
+      unsigned best[8];
+#pragma unroll
+      for (int dy = 0; dy < 5; ++dy) {
+        const int yy = min(max(y + dy - 2, 0), a.H - 1);
+        const int k = (yy * a.W + x) * G + part;
+        const uint4 v0 = row0[k], v1 = row1[k];
+        const unsigned w[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) best[j] = dy ? max(best[j], w[j]) : w[j];
+      }
+      const unsigned ky = (unsigned)(329 - 5 * y);  // code = 5 * (yy - y + 2) + dx = ky - low
+      unsigned kp[4], hv[4], code[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) code[j] = (best[j] >> 16) == KNINF ? 0u : (ky - (best[j] & 0xffffu)) & 0xffu;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        kp[d] = (best[2 * d + 1] & 0xffff0000u) | (best[2 * d] >> 16);
+        hv[d] = kp[d] ^ ((((~kp[d] >> 15) & 0x00010001u) * 0xffffu) | 0x80008000u);
+      }
+      cur[i] = uint4{kp[0], kp[1], kp[2], kp[3]};  // only this thread reads or writes cur[i] in this pass
+      *reinterpret_cast<uint4*>(yb + (size_t)px * a.ld + part * 8) = uint4{hv[0], hv[1], hv[2], hv[3]};
+      if (ab)
+        *reinterpret_cast<uint2*>(ab + (size_t)px * a.C + part * 8) =
+            uint2{code[0] | code[1] << 8 | code[2] << 16 | code[3] << 24, code[4] | code[5] << 8 | code[6] << 16 | code[7] << 24};
     }
     __syncthreads();
   }
@@ -614,6 +729,19 @@ extern "C" int dy_sppf_pool3(void* cat, int ld, int C, void* arg0, void* arg1, v
   if (!cg || !cat || ld < 4 * C) return DY_ERR_ARG;
   if ((ld & 7) || ((uintptr_t)cat & 15)) return DY_ERR_ALIGN;
   SppfArgs a{(f16*)cat, {(uint8_t*)arg0, (uint8_t*)arg1, (uint8_t*)arg2}, ld, C, n, h, w, {0, 0, 0}};
+  const size_t lds2 = (size_t)h * w * (cg / 8) * 48 + 16;  // keys + two planes of row words + the flag
+  if (!tensor_ops_v1() && h <= 63 && w <= 63 && lds2 <= 156 * 1024) {
+    static bool attr2[2] = {false, false};
+    if (cg == 16) {
+      if (!attr2[0]) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(sppf_pool3_fwd_v2_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return DY_ERR_LAUNCH; attr2[0] = true; }
+      hipLaunchKernelGGL(sppf_pool3_fwd_v2_kernel<16>, dim3(n * (C / 16)), dim3(SPPF_THREADS), lds2, stream, a);
+    } else {
+      if (!attr2[1]) { if (hipFuncSetAttribute(reinterpret_cast<const void*>(sppf_pool3_fwd_v2_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return DY_ERR_LAUNCH; attr2[1] = true; }
+      hipLaunchKernelGGL(sppf_pool3_fwd_v2_kernel<8>, dim3(n * (C / 8)), dim3(SPPF_THREADS), lds2, stream, a);
+    }
+    DY_CHECK_LAUNCH();
+    return DY_OK;
+  }
   const size_t lds = (size_t)h * w * (cg / 8) * (2 * 16 + 8);
   static bool attr[2] = {false, false};
   if (cg == 16) {
@@ -1104,6 +1232,192 @@ __global__ __launch_bounds__(256) void scalseq_bwd_cols_kernel(SsBwdAllArgs a) {
     }
   }
 }
+// The streaming form of the kernel above (same lanes, same items, same order of every fp32 operation, so partials and dr0 / dr1 / dr2 keep
+// their bits).  What changed is the schedule: the kernel above issued the loads of an item one row at a time (own2 / own1 / own0 / dY, wait,
+// next row: five dependent HBM round trips per item) with 64-bit item arithmetic per lane and 202 VGPRs (2 waves per SIMD, a quarter of its
+// 2,048 blocks resident).  Here CPP and MODE are compile-time, the item arithmetic is 32-bit and wave-uniform, the eleven 16-byte loads of an
+// item are issued before its first use, the channel loop is outermost (a channel's z / gs values are scalars, not 8-float arrays) and the
+// budget is 4 waves per SIMD.  The grid is what is resident (4 blocks per CU); in mode 0 a workgroup walks the "virtual blocks" vb =
+// blockIdx, blockIdx + gridDim, ... of the launch above: virtual block vb takes the items vb * 4 + wave (+ nvb * 4 ...), reduces them alone
+// in the row order of the kernel above and writes partials[vb], so nparts / max_partials mean what they meant.
+static __device__ __forceinline__ half8 ld16(const f16* sbase, unsigned voff) {  // wave-uniform base + the lane's byte offset
+  return *reinterpret_cast<const half8*>(reinterpret_cast<const char*>(sbase) + voff);
+}
+static __device__ __forceinline__ void st16(f16* sbase, unsigned voff, uint4 v) {
+  *reinterpret_cast<uint4*>(reinterpret_cast<char*>(sbase) + voff) = v;
+}
+// (f16)(a * b) as the kernel above computes it: hipcc chose v_fma_mixlo/hi_f16 (a * b + 0, rounded to fp16 ONCE) for every dr store there,
+// which differs from a product rounded to fp32 and then to fp16 in about one value of 10^4; written out so that no compiler choice is left
+// HERE.  The kernel above is the parent's source and its contractions stay the compiler's: should a compiler change them, the bit tests
+// against the switch fail with neither kernel wrong, and the kernel above (kept for the A/B only) is then the one to retire
+static __device__ __forceinline__ void mul_to_f16(int hi, unsigned& pk, float a, float b) {  // hi: a constant once the channel loop is unrolled
+  if (hi) asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(pk) : "v"(a), "v"(b));
+  else asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "+v"(pk) : "v"(a), "v"(b));
+}
+template <int CPP, int MODE>
+__global__ __launch_bounds__(256, 4) void scalseq_bwd_v2_kernel(SsBwdAllArgs a, int nvb) {
+  // Which multiply-adds of the kernel above were contracted is the compiler's choice there; here every fused one is written as fmaf and
+  // nothing else may fuse, so the two kernels round at the same places: z = fma(v, scale, shift); px = fma(xhat, g, px); level 0
+  // fma(-mgx, xhat, g - mg); levels 1 / 2 fma(mgx, -cnt * xhat, tot - cnt * mg) with cnt * mg a product of its own.
+#pragma clang fp contract(off)
+  constexpr int PW = 64 / CPP, ROWS = 256 / CPP, CC = CPP * 8;
+  const int h1 = a.H >> 1, w1 = a.W >> 1, h2 = a.H >> 2, w2 = a.W >> 2;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int part = lane % CPP, col = lane / CPP, c0 = part * 8;
+  // the six coefficient tables live in LDS and are read where they are used: 48 more live registers would not fit the budget (the
+  // compiler spilled them to scratch and waited for every load in flight at each reload)
+  __shared__ float cf[6][CC];
+  if (tid < CC) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cf[k][tid] = a.coef[k * CC + tid];
+    cf[4][tid] = MODE ? a.bwdcoef[tid] : 0.f;
+    cf[5][tid] = MODE ? a.bwdcoef[CC + tid] : 0.f;
+  }
+  __syncthreads();
+  float ps[8], px[8];
+  // a lane's byte offsets inside its item never change: the item's place goes into wave-uniform bases (a column block starts at a multiple
+  // of PW >= 4 columns, so the level-1 / level-2 columns split the same way)
+  const unsigned vo0 = (unsigned)(col * a.ld[0] + c0) * 2u, vody = (unsigned)(col * a.lddy + c0) * 2u;
+  const unsigned vo1 = (unsigned)((col >> 1) * a.ld[1] + c0) * 2u, vo2 = (unsigned)((col >> 2) * a.ld[2] + c0) * 2u;
+  const unsigned vd0 = MODE ? (unsigned)(col * a.lddr[0] + c0) * 2u : 0u, vd1 = MODE ? (unsigned)((col >> 1) * a.lddr[1] + c0) * 2u : 0u;
+  const unsigned vd2 = MODE ? (unsigned)((col >> 2) * a.lddr[2] + c0) * 2u : 0u;
+  const unsigned chunks = (unsigned)(a.W / PW);
+  const unsigned items = (unsigned)a.N * (unsigned)h2 * chunks;  // < 2^31 (checked by the caller)
+  const unsigned nv = MODE ? gridDim.x : (unsigned)nvb;          // mode 1 has no sums to keep apart: one pass over the physical grid
+  __shared__ float red[MODE ? 1 : 2][MODE ? 1 : 256][9];
+  for (unsigned vb = blockIdx.x; vb < nv; vb += gridDim.x) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ps[j] = px[j] = 0.f;
+    for (unsigned it = vb * 4 + (unsigned)wave; it < items; it += nv * 4) {
+      const unsigned xc = it % chunks, t = it / chunks;
+      const int y2 = (int)(t % (unsigned)h2);
+      const long n = (long)(t / (unsigned)h2);
+      const long x0 = (long)(xc * PW);
+      const long lp2 = (n * h2 + y2) * w2 + (x0 >> 2);
+      long lp1[2], pos[4];
+      half8 own2, own1[2], own0[4], g[4];
+      unsigned pk0[4][4] = {}, pk1[2][4] = {}, pk2[4] = {};  // mode 1: dr0 / dr1 / dr2, two channels per register
+      int coff = c0;
+      asm volatile("" : "+v"(coff));  // the coefficient reads stay inside the item (hoisted out of the loop they are spilled again)
+      const float* const cp = &cf[0][0] + coff;
+      float sc[8], sh[8], mean[8], inv[8], mg[8], mgx[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        sc[j] = cp[j]; sh[j] = cp[CC + j]; mean[j] = cp[2 * CC + j]; inv[j] = cp[3 * CC + j];
+        mg[j] = MODE ? cp[4 * CC + j] : 0.f; mgx[j] = MODE ? cp[5 * CC + j] : 0.f;
+      }
+      own2 = ld16(a.r[2] + lp2 * a.ld[2], vo2);
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        lp1[hf] = (n * h1 + (y2 * 2 + hf)) * w1 + (x0 >> 1);
+        own1[hf] = ld16(a.r[1] + lp1[hf] * a.ld[1], vo1);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        pos[q] = (n * a.H + (y2 * 4 + q)) * a.W + x0;
+        own0[q] = ld16(a.r[0] + pos[q] * a.ld[0], vo0);
+        g[q] = ld16(a.dy + pos[q] * a.lddy, vody);
+      }
+      // all eleven loads are in flight before the first wait: every use of them is below this statement (left to itself hipcc sinks some
+      // of the loads into the arithmetic, one HBM round trip each)
+      asm volatile("" : "+v"(own2), "+v"(own1[0]), "+v"(own1[1]), "+v"(own0[0]), "+v"(own0[1]), "+v"(own0[2]), "+v"(own0[3]), "+v"(g[0]), "+v"(g[1]),
+                        "+v"(g[2]), "+v"(g[3]));
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float zz2 = __builtin_fmaf((float)own2[j], sc[j], sh[j]);
+        const float z2 = zz2 > 0.f ? zz2 : 0.1f * zz2;
+        float gs2 = 0.f;
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+          const float zz1 = __builtin_fmaf((float)own1[hf][j], sc[j], sh[j]);
+          const float z1 = zz1 > 0.f ? zz1 : 0.1f * zz1;
+          float gs1 = 0.f;
+#pragma unroll
+          for (int rr = 0; rr < 2; ++rr) {
+            const int q = hf * 2 + rr;
+            const float zz0 = __builtin_fmaf((float)own0[q][j], sc[j], sh[j]);
+            const float z0 = zz0 > 0.f ? zz0 : 0.1f * zz0;
+            int am = 0;  // first maximum wins (max_pool3d over the depth axis), as above
+            float zb = z0;
+            if (z1 > zb) { am = 1; zb = z1; }
+            if (z2 > zb) { am = 2; zb = z2; }
+            const float gg = (float)g[q][j] * (zb > 0.f ? 1.f : 0.1f);
+            const float g0 = am == 0 ? gg : 0.f;
+            gs1 += am == 1 ? gg : 0.f;
+            gs2 += am == 2 ? gg : 0.f;
+            const float xh0 = ((float)own0[q][j] - mean[j]) * inv[j];
+            if (MODE == 0) {
+              ps[j] += g0;
+              px[j] = __builtin_fmaf(xh0, g0, px[j]);
+            } else {
+              mul_to_f16(j & 1, pk0[q][j >> 1], sc[j], __builtin_fmaf(-mgx[j], xh0, g0 - mg[j]));
+            }
+          }
+          const float tot = gs1 + (CPP == 4 ? dpp_read<DY_DPP_ROW_SHL(4)>(gs1) : __shfl_xor(gs1, CPP, 64));
+          const float xh = ((float)own1[hf][j] - mean[j]) * inv[j];
+          if (MODE == 0) {
+            if (!(col & 1)) { ps[j] += tot; px[j] = __builtin_fmaf(xh, tot, px[j]); }
+          } else {
+            mul_to_f16(j & 1, pk1[hf][j >> 1], sc[j], __builtin_fmaf(mgx[j], -4.f * xh, tot - 4.f * mg[j]));
+          }
+        }
+        float tot;
+        if (CPP == 4) {
+          tot = gs2 + dpp_read<DY_DPP_ROW_SHL(4)>(gs2);
+          tot += dpp_read<DY_DPP_ROW_SHL(8)>(tot);
+        } else {
+          tot = gs2 + __shfl_xor(gs2, CPP, 64);
+          tot += __shfl_xor(tot, 2 * CPP, 64);
+        }
+        const float xh = ((float)own2[j] - mean[j]) * inv[j];
+        if (MODE == 0) {
+          if (!(col & 3)) { ps[j] += tot; px[j] = __builtin_fmaf(xh, tot, px[j]); }
+        } else {
+          mul_to_f16(j & 1, pk2[j >> 1], sc[j], __builtin_fmaf(mgx[j], -16.f * xh, tot - 16.f * mg[j]));
+        }
+      }
+      if (MODE) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) st16(a.dr[0] + pos[q] * a.lddr[0], vd0, uint4{pk0[q][0], pk0[q][1], pk0[q][2], pk0[q][3]});
+        if (!(col & 1)) {
+#pragma unroll
+          for (int hf = 0; hf < 2; ++hf) st16(a.dr[1] + lp1[hf] * a.lddr[1], vd1, uint4{pk1[hf][0], pk1[hf][1], pk1[hf][2], pk1[hf][3]});
+        }
+        if (!(col & 3)) st16(a.dr[2] + lp2 * a.lddr[2], vd2, uint4{pk2[0], pk2[1], pk2[2], pk2[3]});
+      }
+    }
+    if constexpr (MODE == 0) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        red[0][tid][j] = ps[j];
+        red[1][tid][j] = px[j];
+      }
+      __syncthreads();
+      if (tid < 2 * CC) {  // one (sum, channel) per thread; the rows in the order of the kernel above, their loads in flight together
+        const int which = tid / CC, c = tid - which * CC, pp = c >> 3, j = c & 7;
+        float sum = 0.f;
+#pragma unroll 16
+        for (int r = 0; r < ROWS; ++r) sum += red[which][r * CPP + pp][j];
+        a.partials[((size_t)vb * 2 + which) * CC + c] = sum;
+      }
+      __syncthreads();  // red is written again for the next virtual block
+    }
+  }
+}
+static int g_scalseq_grid_cap = 0;
+// tests: caps the physical grid of scalseq_bwd_v2_kernel so that a small shape walks several virtual blocks per workgroup (0 = the default,
+// 4 workgroups per CU); returns the previous cap
+extern "C" int dy_scalseq_bwd_grid_cap(int cap) {
+  const int old = g_scalseq_grid_cap;
+  g_scalseq_grid_cap = cap > 0 ? cap : 0;
+  return old;
+}
+template <int CPP>
+static void scalseq_v2_launch(const SsBwdAllArgs& a, int mode, int nvb, int grid, hipStream_t stream) {
+  if (mode) hipLaunchKernelGGL((scalseq_bwd_v2_kernel<CPP, 1>), dim3(grid), dim3(256), 0, stream, a, nvb);
+  else hipLaunchKernelGGL((scalseq_bwd_v2_kernel<CPP, 0>), dim3(grid), dim3(256), 0, stream, a, nvb);
+}
 extern "C" int dy_scalseq_tail_backward_all(const void* r0, int ld0, const void* r1, int ld1, const void* r2, int ld2,
                                             const void* dy, int lddy, void* dr0, int lddr0, void* dr1, int lddr1,
                                             void* dr2, int lddr2, const float* coef, const float* bwdcoef,
@@ -1126,6 +1440,21 @@ extern "C" int dy_scalseq_tail_backward_all(const void* r0, int ld0, const void*
     if (mode == 0 && wblocks > max_partials) wblocks = max_partials;
     if (wblocks < 1) wblocks = 1;
     if (nparts) *nparts = (int)wblocks;
+    const long items = (long)n * (h >> 2) * (w / (64 / cpp));
+    if (!tensor_ops_v1() && items < (1L << 31) - 4 * 2048) {  // the new kernel's item arithmetic is 32-bit
+      // wblocks stays the number of virtual blocks (= partial rows); the physical grid is what is resident
+      const int cap = g_scalseq_grid_cap ? g_scalseq_grid_cap : DY_NUM_CUS * 4;
+      const int grid = wblocks < cap ? (int)wblocks : cap;
+      switch (cpp) {
+        case 1: scalseq_v2_launch<1>(a, mode, (int)wblocks, grid, stream); break;
+        case 2: scalseq_v2_launch<2>(a, mode, (int)wblocks, grid, stream); break;
+        case 4: scalseq_v2_launch<4>(a, mode, (int)wblocks, grid, stream); break;
+        case 8: scalseq_v2_launch<8>(a, mode, (int)wblocks, grid, stream); break;
+        default: scalseq_v2_launch<16>(a, mode, (int)wblocks, grid, stream); break;
+      }
+      DY_CHECK_LAUNCH();
+      return DY_OK;
+    }
     hipLaunchKernelGGL(scalseq_bwd_cols_kernel, dim3((int)wblocks), dim3(256), 0, stream, a);
     DY_CHECK_LAUNCH();
     return DY_OK;

@@ -362,6 +362,11 @@ int dy_scalseq_tail_backward_all(const void* r0, int ld0, const void* r1, int ld
                                  const void* dy, int lddy, void* dr0, int lddr0, void* dr1, int lddr1, void* dr2,
                                  int lddr2, const float* coef, const float* bwdcoef, float* partials, int max_partials,
                                  int n, int h, int w, int C, int mode, int* nparts, hipStream_t stream);
+/* The streaming kernel behind dy_scalseq_tail_backward_all runs a resident grid whose workgroups walk the nparts "virtual blocks" in turn.
+ * This caps that physical grid (0 = default, four workgroups per CU) so that a test reaches several virtual blocks per workgroup on a
+ * small shape; results do not depend on it.  Returns the previous cap.  Environment DY_TENSOR_OPS_V1=1 (read at every call) makes
+ * dy_scalseq_tail_backward_all and dy_sppf_pool3 launch the kernels their current ones replaced (same bits). */
+int dy_scalseq_bwd_grid_cap(int cap);
 /* Zoom_cat fine branch nn/extra_modules/block.py:3406-3412: 2x2 max + 2x2 mean to half resolution (h, w = output extent) */
 int dy_zoom_pool(const void* x, int ldx, void* y, int ldy, int n, int h, int w, int C, hipStream_t stream);
 int dy_zoom_pool_backward(const void* x, int ldx, const void* dy, int lddy, void* dx, int lddx, int n, int h, int w, int C,
