@@ -1820,6 +1820,54 @@ class Engine:
             self.tape.append(bwd)
         return self.conv_bn_act(sp_c, xo, out)
 
+    # ---- DySample (reference nn/extra_modules/block.py:3819-3892, style 'lp') ---------------------------------------
+    def dysample(self, sp_off: ConvSpec, s, G, x: Act, out: Act | None = None):
+        """``sample(x, offset(x) * 0.25 + init_pos)``: the 1x1 offset convolution (bias, fp32 output, as LDConv's p_conv runs), then
+        one sampler launch (csrc/dysample.hip).  The backward launch hands ``doff`` to the convolution's weight, bias and input
+        gradient.  A frozen offset convolution leaves out its parameter gradients only: its input gradient W^T doff is part of dX
+        whatever the flags say.  Neither a trainable parameter nor an input that needs a gradient: nothing on the tape."""
+        x = self.dense(x)
+        if not self.L.dy_dysample_supported(x.C, G, s):
+            raise NotImplementedError(f"DySample on {x.C} channels, {G} groups, scale {s}: the sampler takes scale 2 or 4 and channels "
+                                      "that are a multiple of 8 * groups")
+        nch = 2 * G * s * s
+        off = self.transient((x.N, x.H, x.W, nch), torch.float32)
+        self.hold(off)
+        live = self._live(sp_off, x)
+        doff = None
+        if self.tape is not None and live:
+            doff = self.transient((x.N, x.H, x.W, nch), torch.float16)  # written whole by the backward launch before it is read
+            self.hold(doff)
+        if sp_off.trainable or self.tape is None:
+            self.conv_bias(sp_off, x, off.data_ptr(), nch, True, lambda: (doff.data_ptr(), nch))
+        else:
+            if live:
+                self._use(x)
+            self._conv_raw(sp_off, x, off.data_ptr(), nch, DY_EPI_BIAS | DY_EPI_F32OUT, 0, sp_off.bias)
+            if live:
+                self.tape.append(lambda: self._input_grad(sp_off, x, doff.data_ptr(), nch, x.H, x.W))
+        if live:
+            self._use(x)  # the sampler's backward writes x's gradient too
+        y = out if out is not None else self.new_act(x.N, s * x.H, s * x.W, x.C)
+        assert (y.N, y.H, y.W, y.C) == (x.N, s * x.H, s * x.W, x.C)
+        self.call("dy_dysample", x.ptr, x.ld, off.data_ptr(), nch, y.ptr, y.ld, x.N, x.H, x.W, x.C, G, s)
+        if self.tape is not None and not live:
+            self._no_grad(y)
+        elif self.tape is not None:
+            def bwd():
+                assert y.grad_ready()
+                if not x.needs_grad:  # offset gradient only
+                    self.call("dy_dysample_backward", x.ptr, x.ld, off.data_ptr(), nch, y.gptr, y.ld, 0, 0, 0, 0, doff.data_ptr(), nch,
+                              0, 0, x.N, x.H, x.W, x.C, G, s)
+                    return
+                dx32 = self.scratch("ld_dx32", x.npix * x.C * 4)  # touched only when the offsets outgrow the gather radius
+                acc = x.grad_target()
+                self.call("dy_dysample_backward", x.ptr, x.ld, off.data_ptr(), nch, y.gptr, y.ld, x.gptr, x.ld, acc, dx32.data_ptr(),
+                          doff.data_ptr(), nch, self.scratch("ld_maxabs", 16).data_ptr(), int(os.environ.get("DY_DS_RMAX", "2")),
+                          x.N, x.H, x.W, x.C, G, s)
+            self.tape.append(bwd)
+        return y
+
     # ---- loss -----------------------------------------------------------------------------------------------------
     def zero_f32(self, t):
         self.call("dy_fill_zero", t.data_ptr(), t.numel() * t.element_size())

@@ -1,16 +1,17 @@
 """Attentional scale-sequence fusion blocks: Zoom_cat, ScalSeq, Add (drop-in for reference
-nn/extra_modules/block.py:3402-3484), and SPDConv, the space-to-depth down-sampling layer (reference :2497-2507)."""
+nn/extra_modules/block.py:3402-3484), SPDConv, the space-to-depth down-sampling layer (reference :2497-2507), and DySample, the
+learned dynamic up-sampler (reference :3819-3892)."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from ...hip import DY_ACT_LEAKY
+from ...hip import DY_ACT_LEAKY, DY_ACT_NONE
 from ...hip.engine import BN3D_EPS, BN3D_MOM
 from ...hip.runtime import HipModule
 from ..modules.conv import Conv
 
-__all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv")
+__all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv", "DySample")
 
 
 class Zoom_cat(HipModule):
@@ -80,3 +81,44 @@ class SPDConv(HipModule):
             raise ValueError(f"SPDConv (layer {getattr(self, 'i', '?')}) needs a map with even sides, got {x.H}x{x.W}: "
                              "the reference's torch.cat of the four parity views fails on it too")
         return self.conv.forward_act(self.rt.eng.space_to_depth(x), out)
+
+
+class DySample(HipModule):
+    """Learned dynamic up-sampling (reference :3819-3892), style 'lp' without dyscope: a 1x1 ``offset`` convolution (bias, no
+    BatchNorm, no activation) predicts, per channel group and per sub-position of the ``scale`` x ``scale`` output block, where the
+    low-resolution map is sampled bilinearly: at the base pixel + 0.25 * offset + ``init_pos``, clamped to the map
+    (``F.grid_sample(..., padding_mode='border')`` after the reference's normalisation cancels).  ``state_dict`` keys, shapes and
+    initialisation are the reference's; the sampler (csrc/dysample.hip) computes ``init_pos`` in closed form, the buffer is kept for
+    the checkpoints."""
+
+    SUPPORTED = "style='lp', dyscope=False, scale 2 or 4 and in_channels a multiple of 8 * groups"
+
+    def __init__(self, in_channels, scale=2, style="lp", groups=4, dyscope=False):
+        super().__init__()
+        if style != "lp" or dyscope:
+            raise NotImplementedError(f"DySample(style={style!r}, dyscope={dyscope}) is outside the HIP path (supported: {self.SUPPORTED})")
+        if scale not in (2, 4) or groups < 1 or in_channels < 8 * groups or in_channels % (8 * groups):
+            raise NotImplementedError(f"DySample(in_channels={in_channels}, scale={scale}, groups={groups}) is outside the HIP path "
+                                      f"(supported: {self.SUPPORTED})")
+        self.scale, self.style, self.groups = scale, style, groups
+        self.offset = nn.Conv2d(in_channels, 2 * groups * scale ** 2, 1)
+        nn.init.normal_(self.offset.weight, 0.0, 0.001)  # reference normal_init(self.offset, std=0.001) :3837, :3844-3848
+        nn.init.constant_(self.offset.bias, 0.0)
+        self.register_buffer("init_pos", self._init_pos())
+
+    def _init_pos(self):
+        """(1, 2 * groups * scale^2, 1, 1): channel d G s^2 + g s^2 + i s + j holds t[j] for d = 0 (x) and t[i] for d = 1 (y),
+        t[k] = (k - (s - 1) / 2) / s (reference :3856-3858)."""
+        s = self.scale
+        t = (torch.arange(s, dtype=torch.float32) - (s - 1) / 2) / s
+        tx, ty = t.view(1, s).expand(s, s), t.view(s, 1).expand(s, s)
+        return torch.stack([tx, ty]).reshape(2, 1, s * s).repeat(1, self.groups, 1).reshape(1, -1, 1, 1).contiguous()
+
+    def out_hw(self, h, w):
+        return self.scale * h, self.scale * w
+
+    def _build_specs(self, rt):
+        rt.make_spec((id(self), "offset"), self.offset, None, DY_ACT_NONE, 1, 1, name="DySample.offset")
+
+    def forward_act(self, x, out=None):
+        return self.rt.eng.dysample(self.rt.specs[(id(self), "offset")], self.scale, self.groups, x, out)

@@ -338,6 +338,32 @@ int dy_upsample2x(const void* x, int ldx, void* y, int ldy, int n, int h, int w,
  * ldy is no multiple of 8 or a pointer is not 16-byte aligned; nothing is launched then. */
 int dy_space_to_depth(void* x, int ldx, void* y, int ldy, int n, int h, int w, int C, int backward, int accumulate,
                       hipStream_t stream);
+/* DySample's sampling stage, nn/extra_modules/block.py:3856-3879 (style 'lp', no dyscope: ``offset(x) * 0.25 + init_pos``, the grid of
+ * ``sample`` :3860-3870 and ``F.grid_sample(bilinear, align_corners=False, padding_mode='border')`` per channel group :3871-3872).
+ * x: fp16 (n, H, W, C) at pixel stride ldx; off: the RAW fp32 output of the 1x1 offset convolution, (n, H, W, 2 G s^2) at ldoff,
+ * channel d G s^2 + g s^2 + i s + j = coordinate d (0 = x, 1 = y) of group g at sub-position (row i, column j); y: fp16
+ * (n, sH, sW, C) at ldy.  Output pixel (s h + i, s w + j) of group g (channels [g C/G, (g+1) C/G)) is the bilinear sample of x at
+ * (clamp(w + 0.25 o_x + t[j], 0, W-1), clamp(h + 0.25 o_y + t[i], 0, H-1)), t[k] = (k - (s-1)/2) / s -- init_pos in closed form, no
+ * buffer is read.  x and y may be channel slices of wider tensors; no other channel is touched.
+ * dy_dysample_supported: s in {2, 4}, G >= 1, C a multiple of 8 G (host-side, no GPU needed).  DY_ERR_ARG for anything else, a
+ * null pointer or a pitch below its channel count; DY_ERR_ALIGN when ldx / ldy is no multiple of 8 or x / y is not 16-byte
+ * aligned; nothing is launched then. */
+int dy_dysample_supported(int C, int G, int s);
+int dy_dysample(const void* x, int ldx, const float* off, int ldoff, void* y, int ldy, int n, int H, int W, int C, int G, int s,
+                hipStream_t stream);
+/* Backward of dy_dysample (autograd through :3878 and grid_sample's backward).  dy: fp16 gradient of y at lddy.
+ * doff (fp16, (n, H, W, lddoff), channels [0, 2 G s^2), lddoff a multiple of 8): the gradient w.r.t. the RAW convolution output --
+ * 0.25 * sum over the group's channels of dy * d(value)/d(coordinate), zero where the unclamped position is at or beyond 0 / size-1
+ * (grid_sample's border rule) -- written, not accumulated.  NULL: skipped.
+ * dx (fp16, (n, H, W, C) at lddx): the sampler's input gradient, written (accumulate = 0) or added (1), by the contract of
+ * dy_ldconv_sample_backward_gather: a deterministic gather over the base pixels within R <= rmax (1..16) of an input pixel, R from
+ * the largest |0.25 o| of the layer measured on the device into scratch (>= 4 bytes); samples with |0.25 o| > rmax - 1 go through
+ * fp32 atomics into dx32 (n*H*W*C floats, caller-owned, need not be zeroed, untouched when the layer has none) and are folded in
+ * by the gather -- no host decision anywhere; without far samples two calls on the same inputs give the same bits.  NULL: skipped
+ * (dx32 / scratch are not needed then).  The offset convolution's own input gradient is the caller's. */
+int dy_dysample_backward(const void* x, int ldx, const float* off, int ldoff, const void* dy, int lddy, void* dx, int lddx,
+                         int accumulate, float* dx32, void* doff, int lddoff, void* scratch, int rmax, int n, int H, int W, int C,
+                         int G, int s, hipStream_t stream);
 int dy_maxpool5(const void* x, int ldx, void* y, int ldy, void* argmax, int n, int h, int w, int C, hipStream_t stream);
 int dy_maxpool5_backward(const void* dy, int lddy, const void* argmax, void* dx, int lddx, int n, int h, int w, int C,
                          int accumulate, hipStream_t stream);
