@@ -21,6 +21,8 @@ struct BnFinArgs {
   int C;
   float count, eps, momentum;
   int update_running;
+  int ldp;  // floats between the two sums of a partial row (>= C: the convolution's rows are round16(cout) wide)
+  long long* nbt;  // optional: nn.BatchNorm's num_batches_tracked, incremented once per launch (dy_bn_finalize_ld)
 };
 
 __global__ __launch_bounds__(256) void bn_finalize_kernel(BnFinArgs a) {
@@ -30,8 +32,8 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(BnFinArgs a) {
     if (!a.part[k]) continue;
     double t1 = 0.0, t2 = 0.0;
     for (int i = tid; i < a.nparts[k]; i += 256) {
-      t1 += a.part[k][((size_t)i * 2 + 0) * a.C + c];
-      t2 += a.part[k][((size_t)i * 2 + 1) * a.C + c];
+      t1 += a.part[k][((size_t)i * 2 + 0) * a.ldp + c];
+      t2 += a.part[k][((size_t)i * 2 + 1) * a.ldp + c];
     }
     s1 += t1 * a.pweight[k];
     s2 += t2 * a.pweight[k];
@@ -61,6 +63,7 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(BnFinArgs a) {
       const double unbiased = a.count > 1.f ? var * a.count / (a.count - 1.0) : var;
       a.running_mean[c] = (1.f - a.momentum) * a.running_mean[c] + a.momentum * (float)mean;
       a.running_var[c] = (1.f - a.momentum) * a.running_var[c] + a.momentum * (float)unbiased;
+      if (a.nbt && c == 0) *a.nbt += 1;
     }
   }
 }
@@ -70,7 +73,20 @@ extern "C" int dy_bn_finalize(const float* p0, int n0, float w0, const float* p1
                               float* running_var, float* coef, int C, float count, float eps, float momentum,
                               int update_running, hipStream_t stream) {
   BnFinArgs a{{p0, p1, p2}, {n0, n1, n2}, {w0, w1, w2}, gamma, beta, running_mean, running_var, coef, C, count, eps,
-              momentum, update_running};
+              momentum, update_running, C, nullptr};
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, stream, a);
+  DY_CHECK_LAUNCH();
+  return DY_OK;
+}
+// dy_bn_finalize for ONE partial set whose rows are ldp >= C floats wide (dealyolo_hip.h): any C >= 1; channels [C, ldp) of the rows are
+// never read, and gamma / beta / the running statistics / coef [4][C] are touched for the C real channels only; with update_running,
+// *num_batches_tracked (may be NULL) counts the launch, as nn.BatchNorm's training forward does
+extern "C" int dy_bn_finalize_ld(const float* part, int nparts, int ldp, const float* gamma, const float* beta, float* running_mean,
+                                 float* running_var, float* coef, int C, float count, float eps, float momentum, int update_running,
+                                 long long* num_batches_tracked, hipStream_t stream) {
+  if (C < 1 || ldp < C || nparts < 1 || !part || !gamma || !beta || !coef || (update_running && (!running_mean || !running_var))) return DY_ERR_ARG;
+  BnFinArgs a{{part, nullptr, nullptr}, {nparts, 0, 0}, {1.f, 0.f, 0.f}, gamma, beta, running_mean, running_var, coef, C, count, eps,
+              momentum, update_running, ldp, update_running ? num_batches_tracked : nullptr};
   hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(256), 0, stream, a);
   DY_CHECK_LAUNCH();
   return DY_OK;
@@ -683,12 +699,12 @@ extern "C" int dy_bn_act_bwd_reduce_rows(const void* dy, int lddy, const void* x
 // per-channel means pass 2 needs.  bwdcoef = [2][C]: mean_g, mean_gxhat.
 __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* partials, int nparts, float* dgamma,
                                                               float* dbeta, float* bwdcoef, int C, float count,
-                                                              int accumulate) {
+                                                              int accumulate, int ldp) {
   const int c = blockIdx.x, tid = threadIdx.x;
   double s1 = 0.0, s2 = 0.0;
   for (int i = tid; i < nparts; i += 256) {
-    s1 += partials[((size_t)i * 2 + 0) * C + c];
-    s2 += partials[((size_t)i * 2 + 1) * C + c];
+    s1 += partials[((size_t)i * 2 + 0) * ldp + c];
+    s2 += partials[((size_t)i * 2 + 1) * ldp + c];
   }
   __shared__ double r1[256], r2[256];
   r1[tid] = s1;
@@ -712,7 +728,17 @@ __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float* parti
 extern "C" int dy_bn_bwd_finalize(const float* partials, int nparts, float* dgamma, float* dbeta, float* bwdcoef, int C,
                                   float count, int accumulate, hipStream_t stream) {
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, stream, partials, nparts, dgamma, dbeta, bwdcoef, C,
-                     count, accumulate);
+                     count, accumulate, C);
+  DY_CHECK_LAUNCH();
+  return DY_OK;
+}
+// dy_bn_bwd_finalize over partial rows ldp >= C floats wide (what dy_bn_act_bwd_reduce_c writes: ldp = round8(C)); dgamma / dbeta /
+// bwdcoef [2][C] are written for the C real channels only
+extern "C" int dy_bn_bwd_finalize_ld(const float* partials, int nparts, int ldp, float* dgamma, float* dbeta, float* bwdcoef, int C,
+                                     float count, int accumulate, hipStream_t stream) {
+  if (C < 1 || ldp < C || nparts < 1 || !partials || !bwdcoef) return DY_ERR_ARG;
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(C), dim3(256), 0, stream, partials, nparts, dgamma, dbeta, bwdcoef, C,
+                     count, accumulate, ldp);
   DY_CHECK_LAUNCH();
   return DY_OK;
 }
@@ -816,6 +842,230 @@ extern "C" int dy_bn_act_bwd_apply_acc(const void* dy, int lddy, const void* x, 
   if (act == DY_ACT_SILU) hipLaunchKernelGGL((bn_act_bwd_apply_kernel<DY_ACT_SILU, true>), grid, dim3(256), lds, stream, a);
   else if (act == DY_ACT_LEAKY) hipLaunchKernelGGL((bn_act_bwd_apply_kernel<DY_ACT_LEAKY, true>), grid, dim3(256), lds, stream, a);
   else hipLaunchKernelGGL((bn_act_bwd_apply_kernel<DY_ACT_NONE, true>), grid, dim3(256), lds, stream, a);
+  DY_CHECK_LAUNCH();
+  return DY_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- any channel count
+// The three streaming passes for a tensor whose LOGICAL width C is any number >= 1 (Detect's class branch is max(ch[0], min(nc, 100))
+// wide: reference nn/modules/head.py:36).  The tensors keep the file's shape -- physical pixel stride a multiple of 8, one 16-byte
+// granule per lane -- and the last granule is ragged: its lanes c >= C are PAD lanes.
+//   * a pad lane that is read (the raw conv output's are never written: the conv masks its stores at channel granularity) is dropped
+//     by a select before anything is computed from it, so a stale NaN / Inf pattern cannot reach a sum or a neighbouring lane;
+//   * a pad lane that is written (y, d(raw)) gets +0.0, so the convolution that reads the tensor next multiplies zeros;
+//   * per-channel vectors (coef [4][C], bwdcoef [2][C]) are the layer's own, C long: never indexed at c >= C.
+// Pixel-to-lane mapping, trip structure and arithmetic are those of the kernels above at width round8(C), hence the same bits on the
+// real channels (and for C % 8 == 0 the same bits altogether).  The three-launch form only: no accumulator prologue, no planes.
+static __device__ __forceinline__ half8 keep_lanes(const half8& v, int nv) {
+  half8 o;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) o[j] = j < nv ? v[j] : (f16)0.f;
+  return o;
+}
+
+template <int ACT>
+__global__ __launch_bounds__(256) void bn_act_apply_c_kernel(ApplyArgs a) {
+  const int cpp = (a.C + 7) >> 3, rows = 256 / cpp;
+  const int part = threadIdx.x % cpp, row = threadIdx.x / cpp, c0 = part * 8;
+  if (row >= rows) return;
+  const int nv = a.C - c0 < 8 ? a.C - c0 : 8;  // real channels of this thread's granule (>= 1)
+  float sc[8], sh[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    sc[j] = j < nv ? a.coef[c0 + j] : 0.f;
+    sh[j] = j < nv ? a.coef[a.C + c0 + j] : 0.f;
+  }
+  auto at = [&](long p) { return a.rev ? a.npix - 1 - p : p; };
+  auto one = [&](long pix, const half8& xv) {
+    pix = at(pix);
+    half8 rv;
+    if (a.res) rv = *reinterpret_cast<const half8*>(a.res + pix * a.ldr + c0);
+    half8 out;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float z = act_fwd_t<ACT>((float)xv[j] * sc[j] + sh[j]);
+      if (a.res) z += (float)rv[j];
+      out[j] = (f16)z;
+    }
+    *reinterpret_cast<half8*>(a.y + pix * a.ldy + c0) = keep_lanes(out, nv);
+  };
+  const long step = (long)gridDim.x * rows;
+  long pix = (long)blockIdx.x * rows + row;
+  for (; pix + step < a.npix; pix += 2 * step) {
+    const half8 x0 = *reinterpret_cast<const half8*>(a.x + at(pix) * a.ldx + c0);
+    const half8 x1 = *reinterpret_cast<const half8*>(a.x + at(pix + step) * a.ldx + c0);
+    one(pix, x0);
+    one(pix + step, x1);
+  }
+  if (pix < a.npix) one(pix, *reinterpret_cast<const half8*>(a.x + at(pix) * a.ldx + c0));
+}
+
+extern "C" int dy_bn_act_apply_c(const void* x, int ldx, const void* res, int ldr, void* y, int ldy, const float* coef, long npix,
+                                 int C, int act, hipStream_t stream) {
+  const int Cp = (C + 7) & ~7;
+  if (C < 1 || (ldx & 7) || (ldy & 7) || (res && (ldr & 7)) || ldx < Cp || ldy < Cp || (res && ldr < Cp)) return DY_ERR_ALIGN;
+  if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)res & 15)) return DY_ERR_ALIGN;
+  if ((Cp >> 3) > 256 || !coef) return DY_ERR_ARG;
+  const int rev = ew_reverse();
+  ApplyArgs a{(const f16*)x, (const f16*)res, (f16*)y, coef, ldx, ldr, ldy, C, act, npix, rev & 1};
+  const dim3 grid(ew_blocks(npix, Cp, "DY_EW_BLOCKS_APPLY", 8192));
+  DY_ACT_DISPATCH(bn_act_apply_c_kernel, grid, stream, a);
+  DY_CHECK_LAUNCH();
+  return DY_OK;
+}
+
+// backward pass 1 (bn_act_bwd_reduce_kernel without the shortcut / planes forms); partial rows are round8(C) floats wide, their
+// columns c >= C are never written (dy_bn_bwd_finalize_ld never reads them)
+template <int ACT>
+__global__ __launch_bounds__(256) void bn_act_bwd_reduce_c_kernel(BwdRedArgs a) {
+  const int Cp = (a.C + 7) & ~7, cpp = Cp >> 3, rows = 256 / cpp, tid = threadIdx.x;
+  const int part = tid % cpp, row = tid / cpp, c0 = part * 8;
+  const int nv = a.C - c0 < 8 ? a.C - c0 : 8;  // real channels of this thread's granule: >= 1 for every thread (c0 < round8(C))
+  const int bx = blockIdx.x, nb = gridDim.x;
+  f32x2 sg[4], sgx[4], sc[4], sh[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    sg[j] = sgx[j] = (f32x2){0.f, 0.f};
+    sc[j] = (f32x2){2 * j < nv ? a.coef[c0 + 2 * j] : 0.f, 2 * j + 1 < nv ? a.coef[c0 + 2 * j + 1] : 0.f};
+    sh[j] = (f32x2){2 * j < nv ? a.coef[a.C + c0 + 2 * j] : 0.f, 2 * j + 1 < nv ? a.coef[a.C + c0 + 2 * j + 1] : 0.f};
+  }
+  if (row < rows) {
+    const long step = (long)nb * rows;
+    long pix = (long)bx * rows + row;
+    auto at = [&](long p) { return a.rev ? a.npix - 1 - p : p; };
+    auto pair = [](const half8& v, int j) { return (f32x2){(float)v[2 * j], (float)v[2 * j + 1]}; };
+    auto ld8 = [&](const f16* base, long p, int ld) { return keep_lanes(*reinterpret_cast<const half8*>(base + at(p) * ld + c0), nv); };
+    for (; pix + step < a.npix; pix += 2 * step) {
+      const half8 dv0 = ld8(a.dy, pix, a.lddy);
+      const half8 xv0 = ld8(a.x, pix, a.ldx);
+      const half8 dv1 = ld8(a.dy, pix + step, a.lddy);
+      const half8 xv1 = ld8(a.x, pix + step, a.ldx);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f32x2 x0 = pair(xv0, j), x1 = pair(xv1, j);
+        const f32x2 g0 = pair(dv0, j) * act_grad2<ACT>(__builtin_elementwise_fma(x0, sc[j], sh[j]));
+        const f32x2 g1 = pair(dv1, j) * act_grad2<ACT>(__builtin_elementwise_fma(x1, sc[j], sh[j]));
+        sg[j] += g0 + g1;
+        sgx[j] += __builtin_elementwise_fma(g0, x0, g1 * x1);
+      }
+    }
+    if (pix < a.npix) {
+      const half8 dv = ld8(a.dy, pix, a.lddy);
+      const half8 xv = ld8(a.x, pix, a.ldx);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const f32x2 x = pair(xv, j);
+        const f32x2 g = pair(dv, j) * act_grad2<ACT>(__builtin_elementwise_fma(x, sc[j], sh[j]));
+        sg[j] += g;
+        sgx[j] += g * x;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const bool real = 2 * j + k < nv;
+        const float mean = real ? a.coef[2 * a.C + c0 + 2 * j + k] : 0.f, inv = real ? a.coef[3 * a.C + c0 + 2 * j + k] : 0.f;
+        sgx[j][k] = (sgx[j][k] - mean * sg[j][k]) * inv;
+      }
+  }
+  __shared__ float red[2][256][8 + 1];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    red[0][tid][j] = sg[j >> 1][j & 1];
+    red[1][tid][j] = sgx[j >> 1][j & 1];
+  }
+  __syncthreads();
+  for (int i = tid; i < 2 * a.C; i += 256) {
+    const int which = i / a.C, c = i - which * a.C, pp = c >> 3, j = c & 7;
+    float s = 0.f;
+    for (int r = 0; r < rows; ++r) s += red[which][r * cpp + pp][j];
+    a.partials[((size_t)bx * 2 + which) * Cp + c] = s;
+  }
+}
+
+extern "C" int dy_bn_act_bwd_reduce_c(const void* dy, int lddy, const void* x, int ldx, const float* coef, float* partials,
+                                      int max_partials, long npix, int C, int act, int* nparts, hipStream_t stream) {
+  const int Cp = (C + 7) & ~7;
+  if (C < 1 || C > 2048 || (ldx & 7) || (lddy & 7) || ldx < Cp || lddy < Cp || ((uintptr_t)x & 15) || ((uintptr_t)dy & 15)) return DY_ERR_ALIGN;
+  const int cpp = Cp >> 3;
+  if (cpp > 256 || !coef || !partials || max_partials < 1) return DY_ERR_ARG;
+  const int rows = 256 / cpp;
+  long blocks = (npix + (long)rows * 8 - 1) / ((long)rows * 8);
+  if (blocks > max_partials) blocks = max_partials;
+  static const long bcap = getenv("DY_EW_BLOCKS_BRED") ? atol(getenv("DY_EW_BLOCKS_BRED")) : 1024;
+  if (blocks > bcap) blocks = bcap;
+  if (blocks < 1) blocks = 1;
+  if (nparts) *nparts = (int)blocks;
+  const int rev = ew_reverse();
+  BwdRedArgs a{(const f16*)dy, (const f16*)x, coef, partials, lddy, ldx, C, act, npix, (rev >> 2) & 1, nullptr, nullptr, 0, 0};
+  DY_ACT_DISPATCH(bn_act_bwd_reduce_c_kernel, dim3((int)blocks), stream, a);
+  DY_CHECK_LAUNCH();
+  return DY_OK;
+}
+
+// backward pass 2 (bn_act_bwd_apply_kernel, finished coefficients): d(raw) for the real channels, +0.0 in the pad lanes
+template <int ACT>
+__global__ __launch_bounds__(256) void bn_act_bwd_apply_c_kernel(BwdApplyArgs a) {
+  const int cpp = (a.C + 7) >> 3, rows = 256 / cpp;
+  const int part = threadIdx.x % cpp, row = threadIdx.x / cpp, c0 = part * 8;
+  if (row >= rows) return;
+  const int nv = a.C - c0 < 8 ? a.C - c0 : 8;
+  float sc[8], sh[8], kb[8], kc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const bool real = j < nv;
+    sc[j] = real ? a.coef[c0 + j] : 0.f;
+    sh[j] = real ? a.coef[a.C + c0 + j] : 0.f;
+    const float mean = real ? a.coef[2 * a.C + c0 + j] : 0.f, inv = real ? a.coef[3 * a.C + c0 + j] : 0.f;
+    const float mg = (a.frozen_stats || !real) ? 0.f : a.bwdcoef[c0 + j];
+    const float mgx = (a.frozen_stats || !real) ? 0.f : a.bwdcoef[a.C + c0 + j];
+    kb[j] = sc[j] * inv * mgx;
+    kc[j] = sc[j] * mg - kb[j] * mean;
+  }
+  auto at = [&](long p) { return a.rev ? a.npix - 1 - p : p; };
+  auto one = [&](long pix, const half8& dv, const half8& xv) {
+    pix = at(pix);
+    *reinterpret_cast<half8*>(a.dx + pix * a.lddx + c0) = keep_lanes(bn_bwd_apply8<ACT>(dv, xv, sc, sh, kb, kc), nv);
+  };
+  const long step = (long)gridDim.x * rows;
+  long pix = (long)blockIdx.x * rows + row;
+  for (; pix + step < a.npix; pix += 2 * step) {
+    const half8 d0 = *reinterpret_cast<const half8*>(a.dy + at(pix) * a.lddy + c0);
+    const half8 x0 = *reinterpret_cast<const half8*>(a.x + at(pix) * a.ldx + c0);
+    const half8 d1 = *reinterpret_cast<const half8*>(a.dy + at(pix + step) * a.lddy + c0);
+    const half8 x1 = *reinterpret_cast<const half8*>(a.x + at(pix + step) * a.ldx + c0);
+    one(pix, d0, x0);
+    one(pix + step, d1, x1);
+  }
+  if (pix < a.npix)
+    one(pix, *reinterpret_cast<const half8*>(a.dy + at(pix) * a.lddy + c0), *reinterpret_cast<const half8*>(a.x + at(pix) * a.ldx + c0));
+}
+
+extern "C" int dy_bn_act_bwd_apply_c(const void* dy, int lddy, const void* x, int ldx, void* dx, int lddx, const float* coef,
+                                     const float* bwdcoef, long npix, int C, int act, int frozen_stats, hipStream_t stream) {
+  const int Cp = (C + 7) & ~7;
+  if (C < 1 || (ldx & 7) || (lddy & 7) || (lddx & 7) || ldx < Cp || lddy < Cp || lddx < Cp) return DY_ERR_ALIGN;
+  if (((uintptr_t)x & 15) || ((uintptr_t)dy & 15) || ((uintptr_t)dx & 15)) return DY_ERR_ALIGN;
+  if ((Cp >> 3) > 256 || !coef || (!frozen_stats && !bwdcoef)) return DY_ERR_ARG;
+  const int rev = ew_reverse();
+  BwdApplyArgs a{(const f16*)dy, (const f16*)x, (f16*)dx, coef, bwdcoef, lddy, ldx, lddx, C, act, frozen_stats, npix, (rev >> 1) & 1,
+                 nullptr, nullptr, nullptr, 1.f};
+  const dim3 grid(ew_blocks(npix, Cp, "DY_EW_BLOCKS_BAPPLY", 512));
+  DY_ACT_DISPATCH(bn_act_bwd_apply_c_kernel, grid, stream, a);
+  DY_CHECK_LAUNCH();
+  return DY_OK;
+}
+
+// a per-channel fp32 vector of n entries copied into one of n_pad >= n with zeros behind it (the bias of a fused Conv whose width is
+// not a multiple of 8: the convolution then runs over round8(cout) rows and its epilogue stores SiLU(0 + 0) = +0.0 in the pad lanes)
+__global__ void pad_f32_kernel(const float* src, int n, float* dst, int n_pad) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_pad) dst[i] = i < n ? src[i] : 0.f;
+}
+extern "C" int dy_pad_f32(const float* src, int n, float* dst, int n_pad, hipStream_t stream) {
+  if (!src || !dst || n < 1 || n_pad < n) return DY_ERR_ARG;
+  hipLaunchKernelGGL(pad_f32_kernel, dim3(cdiv(n_pad, 256)), dim3(256), 0, stream, src, n, dst, n_pad);
   DY_CHECK_LAUNCH();
   return DY_OK;
 }

@@ -125,6 +125,10 @@ BN_DGRED_MAXC = int(os.environ.get("DY_BN_DGRED_MAXC", "64"))
 BN_DGRED_MAXPIX = int(os.environ.get("DY_BN_DGRED_MAXPIX", str(1 << 40)))  # ... and the map size (N*H*W): small maps are latency-bound
 
 
+def round8(c):
+    return (c + 7) // 8 * 8
+
+
 def dev_empty(shape, dtype, device):
     t = torch.empty(shape, dtype=dtype, device=device)
     if POISON and t.numel():
@@ -165,7 +169,9 @@ class Arena:
 
 
 class Storage:
-    """(N,H,W,C) fp16 buffer with an optional gradient twin and a record of which channel ranges of the twin hold data."""
+    """(N,H,W,C) fp16 buffer with an optional gradient twin and a record of which channel ranges of the twin hold data.  ``C`` is the
+    PHYSICAL width, a multiple of 8; an activation whose logical width is not (``Engine.new_act``) is an ``Act`` of that logical width
+    over a storage of round8 channels, and the lanes behind it hold exact zeros wherever a kernel may read them."""
 
     def __init__(self, eng, N, H, W, C, dtype=torch.float16):
         assert C % 8 == 0, f"channel count {C} must be a multiple of 8"
@@ -211,7 +217,7 @@ class Act:
     __slots__ = ("st", "c0", "C", "needs_grad")
 
     def __init__(self, st, c0, C, needs_grad=None):
-        assert c0 % 8 == 0 and C % 8 == 0 and c0 + C <= st.C
+        assert c0 % 8 == 0 and C >= 1 and c0 + round8(C) <= st.C, (c0, C, st.C)
         if needs_grad is None:  # a new view of channels whose producer pruned its backward needs no gradient either
             needs_grad = not (st.nograd and st.grad_free(c0, c0 + C))
         self.st, self.c0, self.C, self.needs_grad = st, c0, C, needs_grad
@@ -220,6 +226,7 @@ class Act:
     H = property(lambda s: s.st.H)
     W = property(lambda s: s.st.W)
     ld = property(lambda s: s.st.C)
+    Cp = property(lambda s: round8(s.C))  # physical width: C plus the zero pad lanes of a ragged last granule
     npix = property(lambda s: s.st.N * s.st.H * s.st.W)
 
     @property
@@ -347,6 +354,9 @@ class SegAct:
         for p in parts:
             flat.extend(p.parts if isinstance(p, SegAct) else [p])
         assert all((q.N, q.H, q.W) == (flat[0].N, flat[0].H, flat[0].W) for q in flat), "concatenation of different map sizes"
+        for q in flat:
+            if q.C % 8:
+                raise NotImplementedError(f"Concat: a member of width {q.C} (not a multiple of 8) can only be read by a Conv or an nn.Conv2d")
         self.parts = flat
         self.C = sum(q.C for q in flat)
 
@@ -649,7 +659,19 @@ class Engine:
         return st
 
     def new_act(self, N, H, W, C):
-        return self.new_storage(N, H, W, C).act()
+        """An activation of LOGICAL width C (any C >= 1) in a storage of its own, round8(C) wide."""
+        return self.new_storage(N, H, W, round8(C)).act(0, C)
+
+    @staticmethod
+    def whole8(op, *xs):
+        """Only Conv / nn.Conv2d consume an activation whose width is not a multiple of 8 (they read its zero pad lanes as
+        channels with zero weights); every other op moves or mixes whole 8-channel granules."""
+        for x in xs:
+            if isinstance(x, SegAct):
+                Engine.whole8(op, *x.parts)
+            elif isinstance(x, (Act, UpAct)) and x.C % 8:
+                raise NotImplementedError(f"{op}: an input of width {x.C} (not a multiple of 8) can only be read by a Conv or an "
+                                          f"nn.Conv2d; {op} has no form for a ragged last 8-channel granule")
 
     def wrap_act(self, t):
         a = Storage.over(self, t).act()
@@ -833,13 +855,25 @@ class Engine:
             return x._full
         return self._concat_copy(x.parts) if isinstance(x, SegAct) else x
 
-    def _conv_raw(self, spec, x, y_ptr, ldy, epi, partials_ptr=0, bias=None):
+    def _conv_raw(self, spec, x, y_ptr, ldy, epi, partials_ptr=0, bias=None, cout=None):
         if isinstance(x, SegAct):
+            assert cout is None and spec.cout == spec.cout_phys, f"{spec.name}: a ragged output width over a segmented input"
             self.call("dy_conv1x1_forward_segs", C.byref(self._segs(x)), spec.wpack.data_ptr(), _ptr(bias), y_ptr, ldy, partials_ptr, x.N, x.H,
                       x.W, x.C, spec.cout, epi)
             return
+        # (the launch takes the PHYSICAL input width: the pad lanes of x hold zeros and so do their columns of the pack)
         self.call("dy_conv_forward", x.ptr, x.ld, spec.wpack.data_ptr(), _ptr(bias), y_ptr, ldy, partials_ptr, x.N, x.H, x.W,
-                  x.C, spec.cout, spec.ks, spec.stride, 1, 0, 0, epi, None)
+                  x.Cp, spec.cout if cout is None else cout, spec.ks, spec.stride, 1, 0, 0, epi, None)
+
+    def _partials(self, nbytes):
+        """Partial-sum rows of the three-launch BatchNorm form: the shared scratch on the main stream; a buffer of the launch's own while a
+        BRANCH is recorded (``cur_sid``: Detect's levels beside each other, DY_HEAD_STREAMS) -- the conv -> finalize pairs of several
+        branches would otherwise meet on one buffer.  (As ``draw`` in ``_conv_bn_act_bwd``.)"""
+        if not self.cur_sid:
+            return self.scratch("partials", nbytes)
+        t = self.transient((nbytes,), torch.uint8)
+        self.hold(t)
+        return t
 
     def out_hw(self, spec, x):
         p = spec.ks // 2
@@ -869,7 +903,14 @@ class Engine:
             x = x.materialize()
         if isinstance(x, UpAct) or (isinstance(x, SegAct) and not self.seg_conv_ok(spec, x)):
             x = self.dense(x)
-        assert x.C == spec.cin_phys, (spec.name, x.C, spec.cin_phys)
+        assert (x.C if isinstance(x, SegAct) else x.Cp) == spec.cin_phys, (spec.name, x.C, spec.cin_phys)
+        ragged = spec.cout != spec.cout_phys  # a ragged last granule: the three-launch form with the any-width kernels (*_c / *_ld)
+        if ragged and isinstance(x, SegAct):
+            x = self.dense(x)  # the segmented 1x1 launch rides the whole-granule epilogue: a ragged output takes the plain launch
+        if ragged and spec.ld is not None:
+            raise NotImplementedError(f"{spec.name}: LDConv of width {spec.cout} (not a multiple of 8)")
+        if ragged and res is not None:
+            raise NotImplementedError(f"{spec.name}: a residual operand of width {spec.cout} (not a multiple of 8)")
         Ho, Wo = self.out_hw(spec, x)
         raw = self.new_act(x.N, Ho, Wo, spec.cout)
         y = out if out is not None else self.new_act(x.N, Ho, Wo, spec.cout)
@@ -903,21 +944,27 @@ class Engine:
             if deferred:
                 self._unapplied[(id(y.st), y.c0, y.C)] = (raw, spec)
         elif self.training:
-            nparts = self.L.dy_conv_num_partials(x.N, x.H, x.W, x.C, spec.cout, spec.ks, spec.stride, 1)
-            part = self.scratch("partials", nparts * 2 * ((spec.cout + 15) // 16 * 16) * 4 + 4096)
+            nparts = self.L.dy_conv_num_partials(x.N, x.H, x.W, spec.cin_phys, spec.cout, spec.ks, spec.stride, 1)
+            cp16 = (spec.cout + 15) // 16 * 16  # the convolution's partial rows are round16(cout) floats wide
+            part = self._partials(nparts * 2 * cp16 * 4 + 4096)
             self._conv_raw(spec, x, raw.ptr, raw.ld, DY_EPI_STATS, part.data_ptr())
-            cp16 = (spec.cout + 15) // 16 * 16
-            assert cp16 == spec.cout, "BN channel counts must be multiples of 16"
-            self.call("dy_bn_finalize", part.data_ptr(), nparts, 1.0, 0, 0, 0.0, 0, 0, 0.0, bn["weight"].data_ptr(),
-                      bn["bias"].data_ptr(), bn["running_mean"].data_ptr(), bn["running_var"].data_ptr(),
-                      spec.coef.data_ptr(), spec.cout, float(npix), spec.bn_eps, spec.bn_mom, 1)
+            if cp16 == spec.cout:
+                self.call("dy_bn_finalize", part.data_ptr(), nparts, 1.0, 0, 0, 0.0, 0, 0, 0.0, bn["weight"].data_ptr(),
+                          bn["bias"].data_ptr(), bn["running_mean"].data_ptr(), bn["running_var"].data_ptr(),
+                          spec.coef.data_ptr(), spec.cout, float(npix), spec.bn_eps, spec.bn_mom, 1)
+            else:
+                self.call("dy_bn_finalize_ld", part.data_ptr(), nparts, cp16, bn["weight"].data_ptr(), bn["bias"].data_ptr(),
+                          bn["running_mean"].data_ptr(), bn["running_var"].data_ptr(), spec.coef.data_ptr(), spec.cout, float(npix),
+                          spec.bn_eps, spec.bn_mom, 1, _ptr(bn.get("nbt")))
         else:
             self._conv_raw(spec, x, raw.ptr, raw.ld, 0)
             self.call("dy_bn_eval_coef", bn["weight"].data_ptr(), bn["bias"].data_ptr(), bn["running_mean"].data_ptr(),
                       bn["running_var"].data_ptr(), spec.coef.data_ptr(), spec.cout, spec.bn_eps)
         if not acc:
-            self.call("dy_bn_act_apply", raw.ptr, raw.ld, 0 if res is None else res.ptr, 0 if res is None else res.ld, y.ptr, y.ld,
-                      spec.coef.data_ptr(), npix, spec.cout, spec.act)
+            # ragged: the raw buffer's pad lanes were never written (the convolution masks its stores per channel); the apply drops
+            # them and writes zeros into y's
+            self.call("dy_bn_act_apply_c" if ragged else "dy_bn_act_apply", raw.ptr, raw.ld, 0 if res is None else res.ptr,
+                      0 if res is None else res.ld, y.ptr, y.ld, spec.coef.data_ptr(), npix, spec.cout, spec.act)
         self._record(live, y, lambda: self._conv_bn_act_bwd(spec, x, raw, y, res))
         return y
 
@@ -1072,8 +1119,15 @@ class Engine:
         elif acc:
             self.call("dy_bn_act_bwd_reduce_acc", y.gptr, y.ld, raw.ptr, raw.ld, spec.coef.data_ptr(), self._acc_ready(spec.acc_b),
                       npix, spec.cout, spec.act, *rg)
+        elif spec.cout != spec.cout_phys:  # a ragged last granule: the any-width kernels (pad lanes of dy and raw dropped where read)
+            part = self._partials(2048 * 2 * spec.cout_phys * 4 + 4096)
+            n = C.c_int(0)
+            self.call("dy_bn_act_bwd_reduce_c", y.gptr, y.ld, raw.ptr, raw.ld, spec.coef.data_ptr(), part.data_ptr(), 2048, npix,
+                      spec.cout, spec.act, C.byref(n))
+            self.call("dy_bn_bwd_finalize_ld", part.data_ptr(), n.value, spec.cout_phys, spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(),
+                      spec.bwdcoef.data_ptr(), spec.cout, float(npix), 0)
         else:
-            part = self.scratch("partials", 2048 * 2 * spec.cout * 4 + 4096)
+            part = self._partials(2048 * 2 * spec.cout * 4 + 4096)
             n = C.c_int(0)
             self.call("dy_bn_act_bwd_reduce", y.gptr, y.ld, raw.ptr, raw.ld, spec.coef.data_ptr(), part.data_ptr(), 2048, npix,
                       spec.cout, spec.act, C.byref(n))
@@ -1097,10 +1151,10 @@ class Engine:
         elif ((self.side_wgrad or side_small) and self.deferred_wgrad is not None) or self.cur_sid:
             # the weight gradient reads this buffer on the side stream while the main stream moves on to the next layer (or this
             # layer's backward runs on a branch beside the main chain's): it cannot be the shared scratch
-            draw = self.transient((npix * spec.cout,), torch.float16)
+            draw = self.transient((npix * spec.cout_phys,), torch.float16)
             self.hold(draw)
         else:
-            draw = self.scratch("draw", npix * spec.cout * 2)
+            draw = self.scratch("draw", npix * spec.cout_phys * 2)
         if bn_wgrad:
             # no apply launch: the weight-gradient kernel forms d(raw) while staging and leaves it in ``draw`` for the dgrad
             bn = (raw, draw, spec.coef.data_ptr(), spec.acc_b.data_ptr(), spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(), float(npix))
@@ -1109,10 +1163,10 @@ class Engine:
         if acc:
             self.call("dy_bn_act_bwd_apply_acc", y.gptr, y.ld, raw.ptr, raw.ld, draw.data_ptr(), spec.cout, spec.coef.data_ptr(),
                       spec.acc_b.data_ptr(), spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(), npix, spec.cout, spec.act, float(npix))
-        else:
-            self.call("dy_bn_act_bwd_apply", y.gptr, y.ld, raw.ptr, raw.ld, draw.data_ptr(), spec.cout, spec.coef.data_ptr(),
-                      spec.bwdcoef.data_ptr(), npix, spec.cout, spec.act, 0)
-        self._conv_bwd(spec, x, draw.data_ptr(), spec.cout, y.H, y.W, side_hint=side_small, wgrad=not frozen)
+        else:  # (d(raw) lives at the physical width; a ragged last granule gets zeros in its pad lanes: the input gradient sums over them)
+            self.call("dy_bn_act_bwd_apply_c" if spec.cout != spec.cout_phys else "dy_bn_act_bwd_apply", y.gptr, y.ld, raw.ptr, raw.ld,
+                      draw.data_ptr(), spec.cout_phys, spec.coef.data_ptr(), spec.bwdcoef.data_ptr(), npix, spec.cout, spec.act, 0)
+        self._conv_bwd(spec, x, draw.data_ptr(), spec.cout_phys, y.H, y.W, side_hint=side_small, wgrad=not frozen)
 
     def _dgrad_only_ok(self, spec, x):
         """The backward of the FROZEN ``spec`` (1x1 Conv + BatchNorm + SiLU, accumulator statistics) over ``x`` is ONE launch that forms
@@ -1257,8 +1311,12 @@ class Engine:
                           spec.ks, praw.ptr, praw.ld, ps.coef.data_ptr(), self._acc_ready(ps.acc_b), ps.cout)
                 self._reduced.add(id(ps))
             else:
+                # (over cin_phys output rows where x has a ragged last granule: the transposed pack's rows behind cin are zeros, so the
+                # pad lanes of the gradient twin are WRITTEN, as zeros, by the whole-granule epilogue; a plain tensor of logical width
+                # cin < cin_phys -- the 3-channel image import -- keeps the masked stores)
+                cin = spec.cin_phys if x.C != x.Cp else spec.cin
                 self.call("dy_conv_forward", dy_ptr, lddy, spec.wpack_t.data_ptr(), 0, x.gptr, x.ld, 0, x.N, Ho, Wo,
-                          spec.cout_phys, spec.cin, spec.ks, 1, spec.stride, x.H, x.W, DY_EPI_ACCUM if acc else 0, None)
+                          spec.cout_phys, cin, spec.ks, 1, spec.stride, x.H, x.W, DY_EPI_ACCUM if acc else 0, None)
 
     deferred_wgrad = None
     tape_mark = None  # index into the tape where the neck + head begin (set by BaseModel.forward_act while tracing)
@@ -1305,6 +1363,18 @@ class Engine:
         Ho, Wo = self.out_hw(spec, x)
         y = out if out is not None else self.new_act(x.N, Ho, Wo, spec.cout)
         epi = DY_EPI_BIAS | (DY_EPI_SILU if spec.act == DY_ACT_SILU else 0)
+        if spec.cout != spec.cout_phys:
+            if isinstance(x, SegAct):
+                x = self.dense(x)  # (the segmented launch takes no output width of its own: the plain launch over one tensor)
+            # a ragged last granule: the launch runs over cout_phys rows -- the pack's rows behind cout are zeros, the bias is read from a
+            # zero-padded copy -- so its whole-granule epilogue stores act(0 + 0) = +0.0 in the pad lanes of y
+            if res is not None:
+                raise NotImplementedError(f"{spec.name}: a residual operand of width {spec.cout} (not a multiple of 8)")
+            if getattr(spec, "bias_pad", None) is None:
+                spec.bias_pad = self.f32(spec.cout_phys, 0.0)
+            self.call("dy_pad_f32", spec.bias.data_ptr(), spec.cout, spec.bias_pad.data_ptr(), spec.cout_phys)
+            self._conv_raw(spec, x, y.ptr, y.ld, epi, 0, spec.bias_pad, cout=spec.cout_phys)
+            return y
         if (res is not None and CONV_RES and spec.act == DY_ACT_SILU and spec.ld is None
                 and self.L.dy_conv_res_supported(x.C, spec.cout, spec.ks, spec.stride)):
             # Bottleneck's shortcut rides on the conv's epilogue (same bits as the store + dy_add pair)
@@ -1492,10 +1562,14 @@ class Engine:
         self.call("dy_bn_act_bwd_reduce", dyp, ld, dyp, ld, ident.data_ptr(), part.data_ptr(), 2048, npix, cp, DY_ACT_NONE,
                   C.byref(n))
         tmp = self.scratch("bwdcoef_tmp", 2 * cp * 4)
-        self.call("dy_bn_bwd_finalize", part.data_ptr(), n.value, 0, spec.gbias.data_ptr(), tmp.data_ptr(), cp, 1.0, accumulate)
+        if cp == spec.cout:
+            self.call("dy_bn_bwd_finalize", part.data_ptr(), n.value, 0, spec.gbias.data_ptr(), tmp.data_ptr(), cp, 1.0, accumulate)
+        else:  # the bias has cout entries, the partial rows cout_phys columns
+            self.call("dy_bn_bwd_finalize_ld", part.data_ptr(), n.value, cp, 0, spec.gbias.data_ptr(), tmp.data_ptr(), spec.cout, 1.0, accumulate)
         self._conv_bwd(spec, x, dyp, ld, Ho, Wo, accumulate, defer=defer)
 
     def upsample2x(self, x: Act, out: Act | None = None):
+        self.whole8("Upsample", x)
         x = self.dense(x)
         if UPSEG and PLANAR and out is None and x.st.buf.dtype == torch.float16 and (self.tape is None or UPSEG_TRAIN):
             # left to the consumer: a Concat member read through the segment table (or Engine.dense, which runs the launch after all)
@@ -1533,6 +1607,7 @@ class Engine:
         """SPDConv's rearrangement (reference nn/extra_modules/block.py:2504-2507): (N, H, W, C) -> (N, H/2, W/2, 4C), channel group
         a + 2b holding the pixels of row parity a and column parity b.  A permutation, so the backward is the same launch the other
         way; an input that needs no gradient (a frozen prefix) leaves nothing on the tape."""
+        self.whole8("SPDConv", x)
         x = self.dense(x)
         if x.H % 2 or x.W % 2 or x.H < 2 or x.W < 2:
             raise ValueError(f"space-to-depth needs an even map, got {x.H}x{x.W}")
@@ -1548,6 +1623,7 @@ class Engine:
         return y
 
     def maxpool5(self, x: Act, out: Act):
+        self.whole8("SPPF", x)
         x = self.dense(x)
         arg = self.transient((x.npix * x.C,), torch.uint8)
         self.hold(arg)
@@ -1563,6 +1639,8 @@ class Engine:
     def sppf_pools(self, cat, c_):
         """SPPF's y1 = m(x), y2 = m(y1), y3 = m(y2) into slices 1..3 of ``cat`` (slice 0 = x): one launch with the map resident in LDS
         when it fits, three dy_maxpool5 launches otherwise.  Reference nn/modules/block.py:166-171."""
+        if c_ % 8:
+            raise NotImplementedError(f"SPPF: a hidden width of {c_} (not a multiple of 8)")
         x = cat.act(0, c_)
         if not (SPPF_FUSED and cat.buf.dtype == torch.float16 and self.L.dy_sppf_pool3_supported(x.H, x.W, c_)):
             for j in range(3):
@@ -1590,6 +1668,7 @@ class Engine:
             self.tape.append(bwd)
 
     def add(self, xs, out: Act | None = None):
+        self.whole8("Add", *xs)
         xs = [self.dense(t) for t in xs]
         a = xs[0]
         y = out if out is not None else self.new_act(a.N, a.H, a.W, a.C)
@@ -1627,6 +1706,7 @@ class Engine:
     def concat(self, xs, out_storage=None):
         """Concat (reference nn/modules/conv.py:338-348).  Inputs already living in consecutive slices of one Storage
         are returned as a view; anything else is copied."""
+        self.whole8("Concat", *xs)
         if any(isinstance(t, SegAct) for t in xs):
             xs = SegAct(xs).parts
         st = xs[0].st
@@ -1676,6 +1756,7 @@ class Engine:
     def zoom_cat(self, xs, out: Act | None = None):
         """Zoom_cat (reference nn/extra_modules/block.py:3402-3412): [maxpool+avgpool of the fine map | middle map | 2x
         nearest of the coarse map] written into one buffer (exact 2x pyramids only)."""
+        self.whole8("Zoom_cat", *xs)
         l, m, s = (self.dense(t) for t in xs)
         assert l.H == 2 * m.H and l.W == 2 * m.W and m.H == 2 * s.H and m.W == 2 * s.W, "Zoom_cat needs exact 2x pyramids"
         y = out if out is not None else self.new_act(m.N, m.H, m.W, l.C + m.C + s.C)
@@ -1709,6 +1790,7 @@ class Engine:
         every scale at its native resolution (a 1x1 conv commutes with nearest up-sampling); BatchNorm3d statistics
         are those of the up-sampled (B,3,H,W) volume, i.e. level l weighs 4**l.  ``res``: a tensor added to the result (the ``Add`` that
         follows ScalSeq in the ASF models, reference nn/extra_modules/block.py:3479-3484, folded into the tail kernel)."""
+        self.whole8("ScalSeq", *ps, res)
         ps = [self.dense(t) for t in ps]
         p3 = ps[0]
         N, H, W, Cc = p3.N, p3.H, p3.W, conv3d.cout
@@ -1782,6 +1864,7 @@ class Engine:
 
     # ---- LDConv (reference nn/modules/conv.py:366-410) -----------------------------------------------------------
     def ldconv(self, sp_p: ConvSpec, sp_c: ConvSpec, pn_i32, Np, stride, x: Act, out: Act | None = None):
+        self.whole8("LDConv", x)
         x = self.dense(x)
         h, w = self.out_hw(sp_p, x)
         off = self.transient((x.N, h, w, 2 * Np), torch.float32)
@@ -1826,6 +1909,7 @@ class Engine:
         one sampler launch (csrc/dysample.hip).  The backward launch hands ``doff`` to the convolution's weight, bias and input
         gradient.  A frozen offset convolution leaves out its parameter gradients only: its input gradient W^T doff is part of dX
         whatever the flags say.  Neither a trainable parameter nor an input that needs a gradient: nothing on the tape."""
+        self.whole8("DySample", x)
         x = self.dense(x)
         if not self.L.dy_dysample_supported(x.C, G, s):
             raise NotImplementedError(f"DySample on {x.C} channels, {G} groups, scale {s}: the sampler takes scale 2 or 4 and channels "

@@ -44,6 +44,9 @@ class C2f(HipModule):
     def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5):
         super().__init__()
         self.c = int(c2 * e)
+        if self.c % 8:  # the chunk and every Bottleneck are channel slices / members of a concatenation: whole 8-channel granules
+            raise NotImplementedError(f"C2f({c1}, {c2}): its hidden width int({c2} * {e}) = {self.c} is not a multiple of 8; the chunk of "
+                                      f"cv1's output and the concatenation cv2 reads move whole 8-channel granules")
         self.cv1 = Conv(c1, 2 * self.c, 1, 1)
         self.cv2 = Conv((2 + n) * self.c, c2, 1)
         self.m = nn.ModuleList(Bottleneck(self.c, self.c, shortcut, g, k=((3, 3), (3, 3)), e=1.0) for _ in range(n))
@@ -86,6 +89,8 @@ class SPPF(HipModule):
         if k != 5:
             raise NotImplementedError("SPPF: only k=5 pooling is implemented on the HIP path")
         c_ = c1 // 2
+        if c_ % 8:  # the pooled copies are channel slices of one buffer
+            raise NotImplementedError(f"SPPF({c1}, {c2}): its hidden width {c1} // 2 = {c_} is not a multiple of 8")
         self.cv1 = Conv(c1, c_, 1, 1)
         self.cv2 = Conv(c_ * 4, c2, 1, 1)
         self.m = nn.MaxPool2d(kernel_size=k, stride=1, padding=k // 2)

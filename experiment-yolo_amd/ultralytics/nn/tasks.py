@@ -87,6 +87,21 @@ def parse_model(d, ch, verbose=True):
         args = [nc if a == "nc" else (None if a == "None" else a) for a in args]
         n_ = n = max(round(n * depth), 1) if n > 1 else n
         fl = [f] if isinstance(f, int) else list(f)
+        # A width that is not a multiple of 8 (a ``Conv [nc, ...]`` layer: the one width make_divisible does not touch) can only be read
+        # by a Conv or by Detect's Conv / nn.Conv2d chains: every other module moves or mixes whole 8-channel granules (hip/engine.py)
+        if i > 0 and m not in (Conv, Detect):
+            for j in fl:
+                if chs[j] % 8:
+                    raise NotImplementedError(f"layer {i} ({mname}) reads layer {j if j >= 0 else i + j}, which is {chs[j]} channels wide: a width "
+                                              f"that is not a multiple of 8 can only feed a Conv or Detect")
+        if m in (LDConv, C2f, SPPF, SPDConv) and args[0] == nc and nc % 8:
+            raise NotImplementedError(f"layer {i} ({mname}) would be {nc} channels wide: only a Conv can produce a width that is not a multiple of 8")
+        if m in (C2f, SPPF) and i > 0:  # their hidden widths (C2f: the chunk of cv1's output, SPPF: the pooled slices) are granules too
+            c2_ = args[0] if args[0] == nc else make_divisible(min(args[0], max_channels) * width, 8)
+            hidden = int(c2_ * 0.5) if m is C2f else chs[f] // 2
+            if hidden % 8:
+                raise NotImplementedError(f"layer {i} ({mname}) has a hidden width of {hidden} channels ({'its output ' + str(c2_) if m is C2f else 'its input ' + str(chs[f])}"
+                                          f" halved): not a multiple of 8")
         if m in (Conv, LDConv, C2f, SPPF, SPDConv):
             c1, c2 = chs[f], args[0]
             if c2 != nc:

@@ -306,6 +306,32 @@ int dy_bn_bwd_finalize(const float* partials, int nparts, float* dgamma, float* 
 int dy_bn_act_bwd_apply(const void* dy, int lddy, const void* x, int ldx, void* dx, int lddx, const float* coef,
                         const float* bwdcoef, long npix, int C, int act, int frozen_stats, hipStream_t stream);
 
+/* ---- the same passes for ANY channel count C >= 1 (Detect's class branch is max(ch[0], min(nc, 100)) wide, nn/modules/head.py:36).
+ * Tensors keep a pixel stride that is a multiple of 8 and >= round8(C); lanes c in [C, round8(C)) of the last 8-channel granule are
+ * PAD lanes.  A pad lane that is READ (the raw conv output: dy_conv_forward masks its fp16 stores at channel granularity, so those
+ * lanes may hold anything) never reaches a result; a pad lane that is WRITTEN (y, dx) gets +0.0, so the convolution that reads the
+ * tensor next multiplies exact zeros; per-channel vectors (gamma, beta, running statistics, coef [4][C], bwdcoef [2][C], dgamma,
+ * dbeta) are C long and never indexed at c >= C.  Same pixel-to-lane mapping and arithmetic as the entry points above at width
+ * round8(C): the real channels carry the same bits, and for C % 8 == 0 so does everything. */
+/* dy_bn_finalize for one partial set whose rows are ldp >= C floats apart ([nparts][2][ldp]: dy_conv_forward's DY_EPI_STATS rows are
+ * round16(cout) wide); with update_running, *num_batches_tracked (int64, may be NULL) is incremented once, as nn.BatchNorm's training
+ * forward does (the entry points above leave that counter to their caller) */
+int dy_bn_finalize_ld(const float* part, int nparts, int ldp, const float* gamma, const float* beta, float* running_mean,
+                      float* running_var, float* coef, int C, float count, float eps, float momentum, int update_running,
+                      long long* num_batches_tracked, hipStream_t stream);
+int dy_bn_act_apply_c(const void* x, int ldx, const void* res, int ldr, void* y, int ldy, const float* coef, long npix, int C,
+                      int act, hipStream_t stream);
+/* partials: [*nparts][2][round8(C)], columns c >= C never written */
+int dy_bn_act_bwd_reduce_c(const void* dy, int lddy, const void* x, int ldx, const float* coef, float* partials, int max_partials,
+                           long npix, int C, int act, int* nparts, hipStream_t stream);
+int dy_bn_bwd_finalize_ld(const float* partials, int nparts, int ldp, float* dgamma, float* dbeta, float* bwdcoef, int C,
+                          float count, int accumulate, hipStream_t stream);
+int dy_bn_act_bwd_apply_c(const void* dy, int lddy, const void* x, int ldx, void* dx, int lddx, const float* coef,
+                          const float* bwdcoef, long npix, int C, int act, int frozen_stats, hipStream_t stream);
+/* dst[0, n) = src, dst[n, n_pad) = 0: the bias of a fused Conv whose width is not a multiple of 8, so that its convolution can run over
+ * round8(cout) rows (zero weight rows) and store SiLU(0) = +0.0 in the pad lanes */
+int dy_pad_f32(const float* src, int n, float* dst, int n_pad, hipStream_t stream);
+
 /* ---- data movement: image import (models/yolo/detect/train.py:57-59), nn.Upsample(2,'nearest') (model YAMLs),
  *      SPPF's MaxPool2d(5,1,2) chain nn/modules/block.py:166-171, Add nn/extra_modules/block.py:3483-3484,
  *      Concat nn/modules/conv.py:338-348, ScalSeq tail nn/extra_modules/block.py:3437-3443. -------------------------- */
