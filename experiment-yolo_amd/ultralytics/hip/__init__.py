@@ -144,6 +144,9 @@ SIGNATURES = {
     "dy_dysample_supported": (i32, [i32, i32, i32]),
     "dy_dysample": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "dy_dysample_backward": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "dy_carafe_supported": (i32, [i32, i32, i32]),
+    "dy_carafe": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "dy_carafe_backward": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp]),
     "dy_maxpool5": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),
     "dy_maxpool5_backward": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dy_bn_group_max": (i32, []),

@@ -1952,6 +1952,38 @@ class Engine:
             self.tape.append(bwd)
         return y
 
+    # ---- CARAFE (reference nn/extra_modules/block.py:3898-3936, k_up 5, scale 2) ------------------------------------
+    def carafe(self, sp_comp: ConvSpec, sp_enc: ConvSpec, x: Act, out: Act | None = None):
+        """``reassemble(x, softmax(pixel_shuffle(enc(comp(x)))))``: the two Convs as any Conv runs (BatchNorm in training, fused after
+        ``fuse()``; ``enc`` is 100 channels wide in a pitch of 104), then one reassembly launch (csrc/carafe.hip).  The backward launch
+        writes the gradient of the logits -- ``enc``'s own closure, next on the reversed tape, takes it from there -- and writes or
+        adds x's.  Frozen Convs whose input needs a gradient keep ``dlogits`` (W^T dL is part of dX) and lose their weight-gradient
+        launches inside their own closures.  Neither a trainable parameter nor an input that needs a gradient: nothing on the tape."""
+        self.whole8("CARAFE", x)
+        x = self.dense(x)
+        if not self.L.dy_carafe_supported(x.C, 5, 2) or sp_enc.cout != 100:
+            raise NotImplementedError(f"CARAFE on {x.C} channels with a {sp_enc.cout}-channel encoder: the reassembly takes k_up 5, scale 2 "
+                                      "(100 encoder channels) and channels that are a multiple of 8")
+        conv = lambda sp, t: self.conv_bn_act(sp, t) if sp.bn is not None else self.conv_fused(sp, t)  # noqa: E731
+        lg = conv(sp_enc, conv(sp_comp, x))  # (read by this op only, lane by lane: no whole8)
+        live = self.tape is None or lg.needs_grad or x.needs_grad
+        if live:
+            self._use(x, lg)
+        y = out if out is not None else self.new_act(x.N, 2 * x.H, 2 * x.W, x.C)
+        assert (y.N, y.H, y.W, y.C) == (x.N, 2 * x.H, 2 * x.W, x.C)
+        self.call("dy_carafe", x.ptr, x.ld, lg.ptr, lg.ld, y.ptr, y.ld, x.N, x.H, x.W, x.C)
+        if self.tape is not None and not live:
+            self._no_grad(y)
+        elif self.tape is not None:
+            def bwd():
+                assert y.grad_ready()
+                assert lg.grad_target() == 0, "CARAFE is the only reader of its logits"
+                dx, ldx, acc = (x.gptr, x.ld, x.grad_target()) if x.needs_grad else (0, 0, 0)
+                self.call("dy_carafe_backward", x.ptr, x.ld, lg.ptr, lg.ld, y.gptr, y.ld, dx, ldx, acc, lg.gptr, lg.ld,
+                          x.N, x.H, x.W, x.C)
+            self.tape.append(bwd)
+        return y
+
     # ---- loss -----------------------------------------------------------------------------------------------------
     def zero_f32(self, t):
         self.call("dy_fill_zero", t.data_ptr(), t.numel() * t.element_size())

@@ -1,3 +1,3 @@
-from .block import Add, DySample, ScalSeq, SPDConv, Zoom_cat
+from .block import CARAFE, Add, DySample, ScalSeq, SPDConv, Zoom_cat
 
-__all__ = ("Add", "DySample", "ScalSeq", "SPDConv", "Zoom_cat")
+__all__ = ("CARAFE", "Add", "DySample", "ScalSeq", "SPDConv", "Zoom_cat")

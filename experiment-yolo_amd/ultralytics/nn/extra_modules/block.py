@@ -1,6 +1,6 @@
 """Attentional scale-sequence fusion blocks: Zoom_cat, ScalSeq, Add (drop-in for reference
-nn/extra_modules/block.py:3402-3484), SPDConv, the space-to-depth down-sampling layer (reference :2497-2507), and DySample, the
-learned dynamic up-sampler (reference :3819-3892)."""
+nn/extra_modules/block.py:3402-3484), SPDConv, the space-to-depth down-sampling layer (reference :2497-2507), DySample, the
+learned dynamic up-sampler (reference :3819-3892), and CARAFE, the content-aware up-sampler (reference :3898-3936)."""
 from __future__ import annotations
 
 import torch
@@ -11,7 +11,7 @@ from ...hip.engine import BN3D_EPS, BN3D_MOM
 from ...hip.runtime import HipModule
 from ..modules.conv import Conv
 
-__all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv", "DySample")
+__all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv", "DySample", "CARAFE")
 
 
 class Zoom_cat(HipModule):
@@ -122,3 +122,28 @@ class DySample(HipModule):
 
     def forward_act(self, x, out=None):
         return self.rt.eng.dysample(self.rt.specs[(id(self), "offset")], self.scale, self.groups, x, out)
+
+
+class CARAFE(HipModule):
+    """Content-aware reassembly of features (arXiv 1905.02188; reference :3898-3936): ``comp`` (1x1 Conv to ``c_mid``) and ``enc``
+    (``k_enc`` x ``k_enc`` Conv to (scale * k_up)^2 = 100 channels, BatchNorm, no activation) predict, per output pixel, a softmax
+    kernel over the 5x5 neighbourhood of its base pixel; the output is that weighted sum (csrc/carafe.hip; the reference's
+    pixel_shuffle / Upsample / Unfold / einsum chain :3926-3935 reduces to it).  ``state_dict`` keys, shapes and initialisation are
+    the reference's: both Convs are this package's ``Conv``; pixel_shuffle, Upsample and Unfold carry no state."""
+
+    SUPPORTED = "k_up=5, scale=2, c a multiple of 8, k_enc 1 or 3"
+
+    def __init__(self, c, k_enc=3, k_up=5, c_mid=64, scale=2):
+        super().__init__()
+        if k_up != 5 or scale != 2 or c < 8 or c % 8 or k_enc not in (1, 3):
+            raise NotImplementedError(f"CARAFE(c={c}, k_enc={k_enc}, k_up={k_up}, scale={scale}) is outside the HIP path "
+                                      f"(supported: {self.SUPPORTED})")
+        self.scale, self.k_up = scale, k_up
+        self.comp = Conv(c, c_mid)
+        self.enc = Conv(c_mid, (scale * k_up) ** 2, k=k_enc, act=False)
+
+    def out_hw(self, h, w):
+        return self.scale * h, self.scale * w
+
+    def forward_act(self, x, out=None):
+        return self.rt.eng.carafe(self.rt.spec(self.comp), self.rt.spec(self.enc), x, out)

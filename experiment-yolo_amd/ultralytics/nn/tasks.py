@@ -20,7 +20,7 @@ import yaml
 
 from ..hip.engine import Act
 from ..hip.runtime import HipModule, Runtime
-from .extra_modules.block import Add, DySample, ScalSeq, SPDConv, Zoom_cat
+from .extra_modules.block import CARAFE, Add, DySample, ScalSeq, SPDConv, Zoom_cat
 from .modules import SPPF, C2f, Concat, Conv, Detect, LDConv
 
 CFG_MODELS = Path(__file__).resolve().parent.parent / "cfg" / "models"
@@ -44,7 +44,7 @@ class Upsample(HipModule):
 
 
 _MODULES = {"Conv": Conv, "LDConv": LDConv, "C2f": C2f, "SPPF": SPPF, "Concat": Concat, "nn.Upsample": Upsample,
-            "ScalSeq": ScalSeq, "Add": Add, "Zoom_cat": Zoom_cat, "Detect": Detect, "SPDConv": SPDConv, "DySample": DySample}
+            "ScalSeq": ScalSeq, "Add": Add, "Zoom_cat": Zoom_cat, "Detect": Detect, "SPDConv": SPDConv, "DySample": DySample, "CARAFE": CARAFE}
 
 
 def guess_model_scale(model_path):
@@ -71,7 +71,7 @@ def yaml_model_load(path):
 
 def parse_model(d, ch, verbose=True):
     """YAML dict -> (nn.Sequential, savelist, per-layer down-sampling) for the hot-path module names
-    (reference tasks.py:780-1062, branches :825-864 -- SPDConv is in that list at :833 --, :905-911, :965-967 for DySample,
+    (reference tasks.py:780-1062, branches :825-864 -- SPDConv is in that list at :833 --, :905-911, :965-967 for DySample and CARAFE,
     :1001-1008)."""
     nc, scales = d.get("nc"), d.get("scales")
     depth, width, max_channels = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0), float("inf")
@@ -118,6 +118,10 @@ def parse_model(d, ch, verbose=True):
             c2 = chs[f]
             args = [c2, *args]
             ds = down[f] / (args[1] if len(args) > 1 else 2)
+        elif m is CARAFE:  # reference tasks.py:965-967 (the same branch); scale 2 is the only one the module takes
+            c2 = chs[f]
+            args = [c2, *args]
+            ds = down[f] / 2
         elif m is Concat:
             c2, ds = sum(chs[x] for x in fl), down[fl[0]]
         elif m is Zoom_cat:
@@ -195,7 +199,7 @@ class BaseModel(HipModule):
                 fl = [m.i + j if j < 0 else j for j in m.f]
                 if len(set(fl)) != len(fl) or any(j in plan for j in fl):
                     continue
-                ok = all(isinstance(self.model[j], (Conv, LDConv, C2f, SPPF, SPDConv, DySample, Upsample, Add, ScalSeq)) for j in fl)
+                ok = all(isinstance(self.model[j], (Conv, LDConv, C2f, SPPF, SPDConv, DySample, CARAFE, Upsample, Add, ScalSeq)) for j in fl)
                 if ok:
                     for pos, j in enumerate(fl):
                         plan[j] = (m.i, pos)
@@ -429,7 +433,7 @@ class DetectionModel(BaseModel):
                 out.append(m.conv.conv.out_channels)
             elif isinstance(m, (C2f, SPPF)):
                 out.append(m.cv2.conv.out_channels)
-            elif isinstance(m, (Upsample, DySample)):
+            elif isinstance(m, (Upsample, DySample, CARAFE)):
                 out.append(out[m.i + m.f if m.f < 0 else m.f])
             elif isinstance(m, (Concat, Zoom_cat)):
                 out.append(sum(out[m.i + j if j < 0 else j] for j in m.f))

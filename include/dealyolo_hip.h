@@ -390,6 +390,24 @@ int dy_dysample(const void* x, int ldx, const float* off, int ldoff, void* y, in
 int dy_dysample_backward(const void* x, int ldx, const float* off, int ldoff, const void* dy, int lddy, void* dx, int lddx,
                          int accumulate, float* dx32, void* doff, int lddoff, void* scratch, int rmax, int n, int H, int W, int C,
                          int G, int s, hipStream_t stream);
+/* CARAFE's reassembly stage, nn/extra_modules/block.py:3926-3935 (pixel_shuffle, softmax over the 25 kernel taps, nearest
+ * up-sampling, Unfold(5, dilation 2, padding 4) and the einsum), for k_up = 5 and scale = 2.
+ * x: fp16 (n, H, W, C) at pixel stride ldx; logits: the encoder's fp16 output (:3924-3925), 100 logical channels at ldl >= 104;
+ * y: fp16 (n, 2H, 2W, C) at ldy.  Y[c, 2h+i, 2w+j] = sum_{a,b} p[5a+b] x[c, h+a-2, w+b-2] with p = softmax over k = 0..24 of
+ * logits[4k + 2i + j, h, w] (maximum subtracted) and x = 0 outside the map.  x and y may be channel slices of wider tensors; no
+ * other channel is touched.  dy_carafe_supported: k_up == 5, scale == 2, C >= 8 a multiple of 8 (host-side, no GPU needed).
+ * DY_ERR_ARG for anything else, a null pointer, n / H / W < 1, a pitch below its width or a map whose 4 n H W reaches 2^31;
+ * DY_ERR_ALIGN when a pitch is no multiple of 8 or a pointer is not 16-byte aligned; nothing is launched then. */
+int dy_carafe_supported(int C, int k_up, int scale);
+int dy_carafe(const void* x, int ldx, const void* logits, int ldl, void* y, int ldy, int n, int H, int W, int C, hipStream_t stream);
+/* Backward of dy_carafe (autograd through :3926-3935).  dy: fp16 gradient of y at lddy.  The softmax weights are recomputed from
+ * the logits, not kept.  dlogits (fp16 (n, H, W, 104) at lddl >= 104, required): p_k (g_k - sum_m p_m g_m) with
+ * g_k = sum_c dy[c, 2h+i, 2w+j] x[c, h+a-2, w+b-2] in the channel order of logits; lanes 100..103 are written as zeros.
+ * dx (fp16 (n, H, W, C) at lddx): written (accumulate = 0) or added to (1); a gather over the <= 25 base pixels x 4 sub-pixels that
+ * read an input pixel.  NULL: that half is skipped.  Fixed summation order, no atomics: two calls give the same bits.  Refusals as
+ * dy_carafe. */
+int dy_carafe_backward(const void* x, int ldx, const void* logits, int ldl, const void* dy, int lddy, void* dx, int lddx,
+                       int accumulate, void* dlogits, int lddl, int n, int H, int W, int C, hipStream_t stream);
 int dy_maxpool5(const void* x, int ldx, void* y, int ldy, void* argmax, int n, int h, int w, int C, hipStream_t stream);
 int dy_maxpool5_backward(const void* dy, int lddy, const void* argmax, void* dx, int lddx, int n, int h, int w, int C,
                          int accumulate, hipStream_t stream);
