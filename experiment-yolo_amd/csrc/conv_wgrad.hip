@@ -69,7 +69,6 @@ static constexpr __host__ __device__ int wg_th(int ks, int stride, int nci, int 
   return (nci * mtc <= 1) ? 8 : ((nci + mtc <= 4) ? 4 : 2);
 }
 
-template <int KS, int STRIDE, int NCI, int MTC, int BNF>
 // (256, 2): two workgroups per CU.  Without the second argument hipcc budgets 512 registers per lane (it put the 36 accumulator
 // tiles of the 64x64 3x3 case into AGPRs: 234 + 188), which leaves ONE workgroup per CU whose four waves stage, wait and
 // multiply in lock-step -- 29 % MFMA utilisation.  With two resident workgroups one stages while the other multiplies.
@@ -82,17 +81,39 @@ template <int KS, int STRIDE, int NCI, int MTC, int BNF>
 // eight that need 137-168.  The compiler reports 100-168 VGPRs, no scratch and 3-4 waves per SIMD for all 32 instantiations
 // (profiles/r08_freeze.md); three workgroups per CU, one staging while two multiply / store, is what the grid is sized for
 // (dgrad_only_columns).
-__global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) ? 1 : 2)) void conv_wgrad_kernel(const WgArgs a) {
+//
+// NW: waves per workgroup.  The 3x3 blocks of NCI * MTC >= 16 tiles (64 x 64 channels: 144 accumulator registers at four waves, one
+// wave per SIMD) also exist with EIGHT waves over the same tiles, LDS images, pitches, prefetch and BatchNorm arithmetic: the 36
+// (ci tile, tap) columns are dealt round-robin to eight waves (CPW 9 -> 5, 80 accumulator registers) and the staging is split over 512
+// threads, so two waves share a SIMD and one multiplies while the other waits on its fragments.  One workgroup per CU and the same
+// grid either way: every accumulator is fed by the same k-steps of the same tiles in the same order, and the slabs keep their bits.
+// (BNF 2's per-thread fp32 bias sums cover other granules with 512 threads: the bias gradient, not the slabs, moves in its last bits.)
+// Eight waves are such a block's default; its four-wave form is the instantiation BNF + 16 (DY_WGRAD_WIDE, wgrad_wide() below), so
+// that the body stays this one kernel and every other instantiation compiles as it did.
+static constexpr __host__ __device__ bool wg_wide_block(int ks, int nci, int mtc) { return ks == 3 && nci * mtc >= 16; }
+#define DY_WGRAD_WIDE_DEFAULT 1
+#define DY_WGRAD_ALT 16
+static constexpr __host__ __device__ int wg_nw(int ks, int nci, int mtc, int bnfx) {
+  return (wg_wide_block(ks, nci, mtc) && (bnfx & ~DY_WGRAD_ALT) <= 2 && (((bnfx & DY_WGRAD_ALT) != 0) != (DY_WGRAD_WIDE_DEFAULT != 0))) ? 8 : 4;
+}
+template <int KS, int STRIDE, int NCI, int MTC, int BNFX>
+__global__ __launch_bounds__(64 * wg_nw(KS, NCI, MTC, BNFX),
+                             (BNFX & 8) ? 3 : (wg_nw(KS, NCI, MTC, BNFX) == 8 ? 2 : (wg_wide_block(KS, NCI, MTC) ? 1 : 2)))
+void conv_wgrad_kernel(const WgArgs a) {
+  constexpr int BNF = BNFX & ~DY_WGRAD_ALT;
+  constexpr int NW = wg_nw(KS, NCI, MTC, BNFX);
+  static_assert(!(BNFX & DY_WGRAD_ALT) || (wg_wide_block(KS, NCI, MTC) && BNF <= 2), "two wave counts: the wide 3x3 blocks only");
+  constexpr int NT = 64 * NW;               // threads per workgroup
   constexpr bool FLAT = (KS == 1);
   constexpr bool DG = (BNF & 4) != 0;            // BNF 5 / 7 = 1 / 3 with the input gradient formed here as well (FLAT, one Cout chunk)
   constexpr bool NOX = (BNF & 8) != 0;           // BNF 13 / 15 = 5 / 7 without the weight gradient: no X operand at all
   static_assert(!NOX || DG, "the form without X exists for the fused input gradient only");
   constexpr bool BN1 = ((BNF & 3) == 1 || (BNF & 3) == 3);   // BatchNorm + SiLU backward formed while staging dY
   constexpr bool XSEG = ((BNF & 3) == 3);        // ... and X is a segmented concatenation (NOX: the dX targets are)
-  static_assert(!DG || (KS == 1 && BN1), "the fused input gradient exists for the 1x1 BatchNorm forms");
+  static_assert(!DG || (KS == 1 && BN1 && NW == 4), "the fused input gradient exists for the 1x1 BatchNorm forms");
   constexpr int TAPS = KS * KS;
   constexpr int NCOL = NCI * TAPS;          // (ci tile, tap) columns of this workgroup
-  constexpr int CPW = (NCOL + 3) / 4;       // columns per wave (round-robin)
+  constexpr int CPW = (NCOL + NW - 1) / NW;       // columns per wave (round-robin)
   constexpr int TH = wg_th(KS, STRIDE, NCI, MTC), TW = 32;
   constexpr int HWX = FLAT ? TH * TW : (TW - 1) * STRIDE + KS;
   constexpr int HHX = FLAT ? 1 : (TH - 1) * STRIDE + KS;
@@ -109,7 +130,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
   __shared__ __attribute__((aligned(16))) char smem[XBYTES + YBYTES];
   char* const sx = smem;
   char* const sy = smem + XBYTES;
-  __shared__ __attribute__((aligned(16))) float sbn[BN1 ? 4 * COUT_C : (BNF == 2 ? 256 * 8 : 4)];  // BNF 1: [sc | sh | kb | kc] of this cout chunk; 2: bias-sum scratch
+  __shared__ __attribute__((aligned(16))) float sbn[BN1 ? 4 * COUT_C : (BNF == 2 ? NT * 8 : 4)];  // BNF 1: [sc | sh | kb | kc] of this cout chunk; 2: bias-sum scratch
   float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // BNF 2: sum over pixels of this thread's dY granule (its channel part is fixed)
   (void)bsum;
   // ---- DG: dX[this Cin chunk][tile pixels] = W^T . d(raw), with the instruction, the orientation (M = Cin rows of the transposed pack,
@@ -142,7 +163,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
   // ---- software pipeline: the next tile's X halo and dY tile are fetched into registers while the current tile is
   // multiplied (one workgroup keeps ~30-60 KB of loads in flight under its MFMAs instead of idling on them)
   constexpr int NGX = HHX * HWX * (CIN_C / 8), NGY = TH * TW * (COUT_C / 8);
-  constexpr int NPX = NOX ? 1 : (NGX + 255) / 256, NPY = (NGY + 255) / 256;
+  constexpr int NPX = NOX ? 1 : (NGX + NT - 1) / NT, NPY = (NGY + NT - 1) / NT;
   uint4 pfx[NPX], pfy[NPY];
   uint4 pfr[BN1 ? NPY : 1];     // BNF: raw conv output granules beside the dy granules
   unsigned roff[BN1 ? NPY : 1]; // their byte offsets in the (raw / draw) geometry
@@ -158,7 +179,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
   (void)pfx; (void)xoff;
 #pragma unroll
   for (int i = 0; i < NPX; ++i) {
-    const int id = tid + i * 256;
+    const int id = tid + i * NT;
     const int pixel = id / CPGX, part = id - pixel * CPGX;
     const bool ok = !NOX && id < NGX && ci0 + part * 8 < a.cin_r8;
     const int hy = FLAT ? 0 : pixel / HWX, hx = FLAT ? pixel : pixel - hy * HWX;
@@ -175,7 +196,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
   if (XIN) {
 #pragma unroll
     for (int i = 0; i < NPX; ++i) {
-      const int id = tid + i * 256;
+      const int id = tid + i * NT;
       const int part = id % CPGX, ch = ci0 + part * 8;
       int sg = 0;
       while (sg + 1 < a.xs.nseg && ch >= a.xs.c_end[sg]) ++sg;
@@ -188,7 +209,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
   }
 #pragma unroll
   for (int i = 0; i < NPY; ++i) {
-    const int id = tid + i * 256;
+    const int id = tid + i * NT;
     const int pixel = id / CPGY, part = id - pixel * CPGY;
     const bool ok = id < NGY && co0 + part * 8 < a.cout_r8;
     const int ty = FLAT ? 0 : pixel / TW, tx = FLAT ? pixel : pixel - ty * TW;
@@ -202,7 +223,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
   if (BN1) {
     // BatchNorm backward coefficients of this cout chunk from the reduce pass's fp64 sums (what bn_act_bwd_apply_kernel<.., true>
     // does in its prologue): dx = sc*g - (kb*x + kc), kb = sc*invstd*mean(g*xhat), kc = sc*mean(g) - kb*mean
-    for (int c = tid; c < COUT_C; c += 256) {
+    for (int c = tid; c < COUT_C; c += NT) {
       const int ch = co0 + c;
       float sc = 0.f, sh = 0.f, kb = 0.f, kc = 0.f;
       if (ch < a.cout) {
@@ -307,7 +328,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
         const float invW = 1.0f / (float)a.W, invH = 1.0f / (float)a.H;
 #pragma unroll
         for (int i = 0; i < NPX; ++i) {
-          const int lp = (tid + i * 256) / CPGX;
+          const int lp = (tid + i * NT) / CPGX;
           long gp = p0 + lp;
           const bool inside = gp < a.npix;
           if ((xup >> i) & 1u) {
@@ -351,7 +372,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
       } else {
 #pragma unroll
         for (int i = 0; i < NPX; ++i) {
-          const int hx = ((tid + i * 256) / CPGX) % HWX;  // recomputed on border tiles only
+          const int hx = ((tid + i * NT) / CPGX) % HWX;  // recomputed on border tiles only
           pfx[i] = ld16(rx, (unsigned)(ix0 + hx) < (unsigned)a.W ? xoff[i] + ox : NEVER);
         }
       }
@@ -361,7 +382,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
       } else {
 #pragma unroll
         for (int i = 0; i < NPY; ++i) {
-          const int tx = ((tid + i * 256) / CPGY) % TW;
+          const int tx = ((tid + i * NT) / CPGY) % TW;
           pfy[i] = ld16(ry, ox0 + tx < a.Wo ? yoff[i] + oy : NEVER);
         }
       }
@@ -375,7 +396,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
         for (int i = 0; i < NPY; ++i) {
           unsigned off = roff[i] == NEVER ? NEVER : roff[i] + ornext;
           if (!xfull) {
-            const int tx = ((tid + i * 256) / CPGY) % TW;
+            const int tx = ((tid + i * NT) / CPGY) % TW;
             off = ox0 + tx < a.Wo ? off : NEVER;
           }
           pfr[i] = ld16(rr, off);
@@ -396,7 +417,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
     __syncthreads();  // previous tile's fragment reads are done
 #pragma unroll
     for (int i = 0; i < NPX; ++i) {
-      const int id = tid + i * 256;
+      const int id = tid + i * NT;
       if (!NOX && id < NGX) *reinterpret_cast<uint4*>(sx + (id / (CIN_C / 8)) * PSX + (id % (CIN_C / 8)) * 16) = pfx[i];
     }
     if (BN1) {
@@ -408,7 +429,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
       const auto rd = __builtin_amdgcn_make_buffer_rsrc(FLAT ? a.draw : a.draw + (size_t)ncur * a.Ho * a.Wo * a.ldraw, 0, (int)nbytes, 0x00020000);
 #pragma unroll
       for (int i = 0; i < NPY; ++i) {
-        const int id = tid + i * 256;
+        const int id = tid + i * NT;
         const int part = id % CPGY;
         const bool valid = (vcur >> i) & 1u;
         const float* cf = sbn + part * 8;
@@ -422,7 +443,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
     } else {
 #pragma unroll
       for (int i = 0; i < NPY; ++i) {
-        const int id = tid + i * 256;
+        const int id = tid + i * NT;
         if (id < NGY) *reinterpret_cast<uint4*>(sy + (id / (COUT_C / 8)) * PSY + (id % (COUT_C / 8)) * 16) = pfy[i];
         if (BNF == 2 && id < NGY) {  // bias gradient = sum of dY over the pixels: taken while the granule passes (zeros outside the map)
           const half8 v = *reinterpret_cast<const half8*>(&pfy[i]);
@@ -462,7 +483,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
       }
     };
     auto load_b = [&](int buf, int r, int c) {
-      const int col = wave + 4 * c;
+      const int col = wave + NW * c;
       if (col < NCOL) {
         const int cit = col / TAPS, tap = col - cit * TAPS;
         const int dy = tap / KS, dx = tap - dy * KS;
@@ -489,7 +510,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
         if (c + 1 < CPW) load_b((lin + 1) & 1, r, c + 1);
         else if (r + 1 < TH) load_b((lin + 1) & 1, r + 1, 0);
         __builtin_amdgcn_sched_barrier(0);
-        if (wave + 4 * c < NCOL) {
+        if (wave + NW * c < NCOL) {
 #pragma unroll
           for (int m = 0; m < MTC; ++m)
             acc[NOX ? 0 : m][NOX ? 0 : c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[r & 1][m], bf[lin & 1], acc[NOX ? 0 : m][NOX ? 0 : c], 0, 0, 0);
@@ -562,7 +583,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
     }
   }
 
-  if (BNF == 2 && ci_chunk == 0) {  // (256 % CPGY == 0 is the launcher's condition: a thread's channel part never changes)
+  if (BNF == 2 && ci_chunk == 0) {  // (NT % CPGY == 0 is the launcher's condition: a thread's channel part never changes)
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 8; ++j) sbn[tid * 8 + j] = bsum[j];
@@ -570,7 +591,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
     if (tid < COUT_C && co0 + tid < a.cout) {
       const int part = tid >> 3, j = tid & 7;
       float t = 0.f;
-      for (int k = part; k < 256; k += CPGY) t += sbn[k * 8 + j];
+      for (int k = part; k < NT; k += CPGY) t += sbn[k * 8 + j];
       unsafeAtomicAdd(const_cast<double*>(a.acc) + (size_t)(blockIdx.x % DY_BN_COPIES) * a.cout + co0 + tid, (double)t);
     }
   }
@@ -579,7 +600,7 @@ __global__ __launch_bounds__(256, (BNF & 8) ? 3 : ((KS == 3 && NCI * MTC >= 16) 
   float* slab = a.slabs + (size_t)blockIdx.x * TAPS * a.cout_p * a.cin_p;
 #pragma unroll
   for (int c = 0; c < CPW; ++c) {
-    const int col = wave + 4 * c;
+    const int col = wave + NW * c;
     if (col < NCOL) {
       const int cit = col / TAPS, tap = col - cit * TAPS;
 #pragma unroll
@@ -697,6 +718,21 @@ extern "C" int dy_wgrad_reduce_batched(const void* descs_device, int n, int tota
   return DY_OK;
 }
 
+// DY_WGRAD_WIDE (read at every call): 1 = the eight-wave form of the wide 3x3 blocks, 0 = their four-wave form, unset = the default
+static bool wgrad_wide() {
+  const char* e = getenv("DY_WGRAD_WIDE");
+  return (e && (e[0] == '0' || e[0] == '1') && !e[1]) ? e[0] == '1' : DY_WGRAD_WIDE_DEFAULT != 0;
+}
+template <int KS, int STRIDE, int NCI, int MTC, int BNF>
+static void launch_wgrad_form(const WgArgs& a, int gx, int gy, hipStream_t s) {
+  if constexpr (wg_wide_block(KS, NCI, MTC) && BNF <= 2) {
+    if (wgrad_wide() != (DY_WGRAD_WIDE_DEFAULT != 0)) {  // the other wave count
+      hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, BNF + DY_WGRAD_ALT>), dim3(gx, gy), dim3(64 * wg_nw(KS, NCI, MTC, BNF + DY_WGRAD_ALT)), 0, s, a);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, BNF>), dim3(gx, gy), dim3(64 * wg_nw(KS, NCI, MTC, BNF)), 0, s, a);
+}
 template <int KS, int STRIDE, int NCI, int MTC>
 static int launch_wgrad(const WgArgs& a, int gx, int gy, hipStream_t s) {
   if (a.wt) {  // the fused input gradient: 1x1 BatchNorm forms whose one Cout chunk is the whole layer (dy_conv1x1_wgrad_dgrad_supported)
@@ -711,10 +747,10 @@ static int launch_wgrad(const WgArgs& a, int gx, int gy, hipStream_t s) {
   } else if (a.raw && a.xs.nseg > 0) {
     if constexpr (KS == 1) hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 3>), dim3(gx, gy), dim3(256), 0, s, a);
     else return DY_ERR_ARG;
-  } else if (a.raw) hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 1>), dim3(gx, gy), dim3(256), 0, s, a);
-  else if (a.acc && MTC != 3) hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 2>), dim3(gx, gy), dim3(256), 0, s, a);
+  } else if (a.raw) launch_wgrad_form<KS, STRIDE, NCI, MTC, 1>(a, gx, gy, s);
+  else if (a.acc && MTC != 3) launch_wgrad_form<KS, STRIDE, NCI, MTC, 2>(a, gx, gy, s);
   else if (a.acc) return DY_ERR_ARG;
-  else hipLaunchKernelGGL((conv_wgrad_kernel<KS, STRIDE, NCI, MTC, 0>), dim3(gx, gy), dim3(256), 0, s, a);
+  else launch_wgrad_form<KS, STRIDE, NCI, MTC, 0>(a, gx, gy, s);
   DY_CHECK_LAUNCH();
   return DY_OK;
 }
@@ -815,12 +851,16 @@ static int conv_wgrad_impl(const void* x, int ldx, const void* dy, int lddy, flo
                            int cin, int cout, int ks, int stride, int accumulate, int ld_taps, int ld_cphys, int ld_cin,
                            hipStream_t stream, const WgBnHost* bn = nullptr);
 
+// the last template argument of the BNF 0 form: a wide 3x3 block's other wave count is BNF + 16 (DY_WGRAD_WIDE)
+static int wgrad_kernel_bnf0(int ks, int nci, int mtc) {
+  return (wg_wide_block(ks, nci, mtc) && wgrad_wide() != (DY_WGRAD_WIDE_DEFAULT != 0)) ? DY_WGRAD_ALT : 0;
+}
 // host-side: the kernel instantiation dy_conv_wgrad launches for this geometry, spelled as rocprofv3 prints it
 extern "C" int dy_wgrad_kernel_name(int cin, int cout, int ks, int stride, char* out, int cap) {
   if (!out || cap < 8) return DY_ERR_ARG;
   int cp, op, nci, mtc;
   wgrad_geometry(cin, cout, ks, stride, &cp, &op, &nci, &mtc);
-  snprintf(out, cap, "conv_wgrad_kernel<%d, %d, %d, %d, 0>", ks, stride, nci, mtc);  // ", 1>": the dy_conv_wgrad_bn form
+  snprintf(out, cap, "conv_wgrad_kernel<%d, %d, %d, %d, %d>", ks, stride, nci, mtc, wgrad_kernel_bnf0(ks, nci, mtc));  // ", 1>": the dy_conv_wgrad_bn form
   return DY_OK;
 }
 
@@ -830,7 +870,7 @@ extern "C" int dy_wgrad_kernel_name_at(int n, int h, int w, int cin, int cout, i
   int cp, op, nci, mtc;
   wgrad_geometry(cin, cout, ks, stride, &cp, &op, &nci, &mtc,
                  (long)n * ((h + 2 * (ks / 2) - ks) / stride + 1) * ((w + 2 * (ks / 2) - ks) / stride + 1));
-  snprintf(out, cap, "conv_wgrad_kernel<%d, %d, %d, %d, 0>", ks, stride, nci, mtc);
+  snprintf(out, cap, "conv_wgrad_kernel<%d, %d, %d, %d, %d>", ks, stride, nci, mtc, wgrad_kernel_bnf0(ks, nci, mtc));
   return DY_OK;
 }
 

@@ -98,6 +98,7 @@ SIGNATURES = {
     "dy_wgrad_workspace": (i32, [i32, i32, i32, i32, i32, i32, i32, ip, lp]),
     "dy_conv_wgrad": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "dy_stem_grid": (i32, [i32, i32, i32]),
+    "dy_stem_pipelined": (i32, [vp, i32]),
     "dy_stem_forward": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, f32, vp]),
     "dy_stem_forward_eval": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
     "dy_stem_wgrad_bn": (i32, [vp, vp, i32, vp, i32, vp, vp, vp, vp, f32, vp, i32, i32, i32, f32, vp]),

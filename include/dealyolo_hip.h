@@ -113,7 +113,9 @@ int dy_conv_kernel_name_at(int cin, int cout, int ks, int stride, int out_w, int
 
 /* ---- weight-gradient half of aten::convolution_backward for the same modules. dw: fp32 OIHW (cout,cin,ks,ks). -- */
 int dy_wgrad_workspace(int n, int h, int w, int cin, int cout, int ks, int stride, int* nslabs, long* slab_elems);
-/* host-side: the kernel instantiation dy_conv_wgrad launches for this geometry, spelled as rocprofv3 prints it */
+/* host-side: the kernel instantiation dy_conv_wgrad launches for this geometry, spelled as rocprofv3 prints it.  The 3x3 block of
+ * 64 x 64 channels exists with eight waves per workgroup (conv_wgrad_kernel<3, 1, 4, 4, BNF>, the default) and with four
+ * (the instantiation BNF + 16): DY_WGRAD_WIDE=0 / 1, read at every call, picks; same slabs, same bits. */
 int dy_wgrad_kernel_name(int cin, int cout, int ks, int stride, char* out, int cap);
 /* the same for a given map: on small maps a workgroup owns a smaller (ci, co) channel block, so that fewer fp32 weight slabs exist */
 int dy_wgrad_kernel_name_at(int n, int h, int w, int cin, int cout, int ks, int stride, char* out, int cap);
@@ -208,8 +210,11 @@ int dy_conv1x1_dgrad_bn(const void* dy, const void* dy2, int lddy, int csplit, c
  * dy_stem_forward writes the raw conv output (N,Ho,Wo,ldraw) fp16 and ADDS the BatchNorm sums into acc [DY_BN_COPIES][2][16]
  * (then dy_bn_act_apply_acc as for any Conv).  dy_stem_wgrad_bn: weight gradient with the BatchNorm / SiLU backward apply inside
  * (as dy_conv_wgrad_bn; no d(raw) output -- the image needs no gradient): slabs [dy_stem_grid()][9][16][16] fp32 for
- * dy_wgrad_reduce_batched (descriptor: cin 3, cout 16, ks 3, stride 2). */
+ * dy_wgrad_reduce_batched (descriptor: cin 3, cout 16, ks 3, stride 2).
+ * The three launches run software-pipelined kernels with 16-byte image loads where w % 4 == 0 and the image base is 16-byte aligned
+ * (dy_stem_pipelined: 1), the plain kernels otherwise or under DY_STEM_V1=1 (read at every call); the results are the same bits. */
 int dy_stem_grid(int n, int h, int w);
+int dy_stem_pipelined(const float* img_nchw, int w);
 int dy_stem_forward(const float* img_nchw, const float* weight, void* raw, int ldraw, double* acc, int n, int h, int w, float mul,
                     hipStream_t stream);
 /* The same stem in eval mode (Conv.forward_fuse, nn/modules/conv.py:57-59; get_FPS.py:49 fuses the model before timing it):
