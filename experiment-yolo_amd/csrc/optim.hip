@@ -226,6 +226,17 @@ static int optimizer_step_impl(float* params, const float* grads, float* mom, fl
   return DY_OK;
 }
 
+// The first two launches of the step on their own: found_inf, the unscaled norm and the clip coefficient (state[2..4]) for an
+// optimizer whose update is not optim_step_kernel's (SOAP, soap.hip).  dy_optimizer_step_seg run afterwards writes the same values.
+extern "C" int dy_grad_norm(const float* grads, long n, const float* hyper, float* state, float* partials, hipStream_t stream) {
+  if (!grads || !hyper || !state || !partials || n <= 0) return DY_ERR_ARG;
+  const int blocks = (int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024);
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(256), 0, stream, grads, n, partials);
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, stream, partials, blocks, hyper, state);
+  DY_CHECK_LAUNCH();
+  return DY_OK;
+}
+
 // The per-step hyper-parameters travel as KERNEL ARGUMENTS (copied at enqueue time), not through a reused pinned host buffer:
 // the host may be many steps ahead of the device, and an asynchronous copy from a buffer the host has since overwritten would
 // hand step i the learning rate of step i+k.

@@ -64,6 +64,12 @@ class DySegs(C.Structure):
     _fields_ = [("nseg", i32), ("c_end", i32 * 8), ("ld", i32 * 8), ("acc", i32 * 8), ("ptr", vp * 8)]
 
 
+class DySoapDesc(C.Structure):
+    """include/dealyolo_hip.h DySoapDesc: one trainable tensor of optimizer='SOAP' (hip/soap.py, SoapTable)."""
+    _fields_ = [("off", i64), ("numel", i64), ("pool_off", i64 * 5), ("group", i32), ("ndim", i32), ("shape", i32 * 5), ("has_q", i32 * 5),
+                ("ord_off", i32 * 5), ("rot_blk", i32 * 5), ("gram_blk", i32 * 5), ("ew_blk", i32), ("reserved", i32)]
+
+
 # name -> (restype, argtypes); every exported symbol of include/dealyolo_hip.h appears here (tests/test_abi.py)
 SIGNATURES = {
     "dy_abi_version": (i32, []),
@@ -209,6 +215,13 @@ SIGNATURES = {
     "dy_optimizer_step": (i32, [vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, i32, vp]),
     "dy_optimizer_step_seg": (i32, [vp, vp, vp, vp, vp, i64, lp, vp, vp, vp, i64, vp, vp, vp, i32, vp]),
     "dy_axpy_f32": (i32, [vp, vp, f32, i64, vp]),
+    "dy_soap_desc_bytes": (i32, []),
+    "dy_grad_norm": (i32, [vp, i64, vp, vp, vp, vp]),
+    "dy_soap_rotate": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, vp]),
+    "dy_soap_gram": (i32, [vp, vp, vp, i32, i32, f32, vp, vp]),
+    "dy_soap_adam": (i32, [vp, vp, vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp]),
+    "dy_soap_apply": (i32, [vp, vp, vp, i32, i32, C.POINTER(f32), C.POINTER(f32), vp, vp]),
+    "dy_soap_permute_v": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp]),
     "dy_scale_img": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "dy_tta_merge": (i32, [i32, C.POINTER(vp), ip, ip, ip, C.POINTER(f32), ip, i32, i32, i32, i32, vp, vp]),
     "dy_bootstrap_ap": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]),
@@ -233,6 +246,8 @@ def lib():
             fn.restype, fn.argtypes = res, args
         if L.dy_segs_bytes() != C.sizeof(DySegs):
             raise RuntimeError(f"{LIB_PATH} lays DySegs out in {L.dy_segs_bytes()} bytes, this binding in {C.sizeof(DySegs)}: rebuild the library")
+        if L.dy_soap_desc_bytes() != C.sizeof(DySoapDesc):
+            raise RuntimeError(f"{LIB_PATH} lays DySoapDesc out in {L.dy_soap_desc_bytes()} bytes, this binding in {C.sizeof(DySoapDesc)}: rebuild the library")
         if L.dy_loss_args_bytes() != C.sizeof(DyLossArgs):  # a stale .so (or a stale binding) would read garbage pointers
             raise RuntimeError(f"{LIB_PATH} was built with a DyLossArgs of {L.dy_loss_args_bytes()} bytes, this binding lays out "
                                f"{C.sizeof(DyLossArgs)}: rebuild the library (make -C experiment-yolo_amd/csrc)")

@@ -47,7 +47,7 @@ class StepPlan:
                                    "ultralytics/hip/__init__.py).  Export it, or import ultralytics before the first torch.cuda call; "
                                    "hipgraph=False / use_graph=False runs the same launch lists eagerly.")
         self.use_graph = use_graph
-        self.soap = optimizer == "SOAP"  # host-driven (hip/soap.py); the flat kernel then only keeps EMA / loss scale / counters
+        self.soap = optimizer == "SOAP"  # hip/soap.py (grouped HIP kernels; host-driven torch ops under DY_SOAP_HIP=0); the flat kernel then only keeps EMA / loss scale / counters
         self.mode = {"SGD": 0, "Adam": 1, "AdamW": 2, "RMSProp": 3, "RAdam": 4, "Adamax": 5, "NAdam": 6, "SOAP": 0}[optimizer]
         if self.soap and use_graph:
             use_graph = self.use_graph = False  # eigh / QR are not captured; SOAP steps run eagerly
@@ -558,10 +558,15 @@ class StepPlan:
 
     def _soap_step(self, grads):
         """optimizer='SOAP' (reference engine/trainer.py:1156-1165): unscale + global-norm clip like ``optimizer_step`` does, then
-        hip/soap.py over views of the flat parameter buffer.  Synchronises (non-finite gradients skip the step, as GradScaler does)."""
+        hip/soap.py over the flat parameter buffer.  The grouped HIP step (``SoapHip``, the default) unscales and clips inside its
+        kernels and reads back one flag; the host-driven ``Soap`` (DY_SOAP_HIP=0) synchronises three times.  Non-finite gradients
+        skip the step either way, as GradScaler does."""
         rt = self.rt
-        self._soap_make()
+        so = self._soap_make()
         g = grads[:rt.n_params_flat]
+        if self._soap_hip:
+            so.step(g, self._hyp["lr"], self._hyp["wd"])
+            return
         if not bool(torch.isfinite(g).all()):
             return  # the kernel below sees the same non-finite gradients and counts the skip
         scale = float(self.state[0])
@@ -572,13 +577,17 @@ class StepPlan:
     def _soap_make(self):
         rt = self.rt
         if getattr(self, "_soap", None) is None:
-            from .soap import Soap
+            from .soap import Soap, SoapHip
             views = []
             for n, p in self.model.named_parameters():
                 if p.requires_grad:
                     views.append((n, rt.param_off[n], p.numel(), tuple(p.shape), rt.param_group[n]))
             self._soap_views = views
-            self._soap = Soap([(rt.flat_p[o:o + k].view(sh), g) for _, o, k, sh, g in views], beta1=self._hyp["momentum"], beta2=0.95)
+            self._soap_hip = os.environ.get("DY_SOAP_HIP", "1") != "0"  # read when the optimizer object is built
+            if self._soap_hip:
+                self._soap = SoapHip(views, rt.flat_p, self.hyper, self.state, self.partials, beta1=self._hyp["momentum"], beta2=0.95)
+            else:
+                self._soap = Soap([(rt.flat_p[o:o + k].view(sh), g) for _, o, k, sh, g in views], beta1=self._hyp["momentum"], beta2=0.95)
             self._soap_apply_pending()
         return self._soap
 
@@ -608,6 +617,9 @@ class StepPlan:
         from .soap import _State
         dev = self.rt.flat_p.device
         mv = lambda t: None if t is None else t.to(dev)  # noqa: E731
+        if self._soap_hip:  # into the pools
+            self._soap.load({i: saved[n] for i, (n, *_r) in enumerate(self._soap_views) if n in saved})
+            return
         for i, (n, o, k, sh, _g) in enumerate(self._soap_views):
             if n in saved:
                 d = saved[n]

@@ -632,6 +632,60 @@ int dy_optimizer_step_seg(float* params, const float* grads, float* mom, float* 
 int dy_set_hyper(float* hyper_dev, const float* host_values16, hipStream_t stream);
 int dy_axpy_f32(float* y, const float* x, float a, long n, hipStream_t stream);
 
+/* ---- optimizer='SOAP': the reference trainer's SOAP class (engine/trainer.py:54-473, built by build_optimizer :1156-1165) over the
+ *      flat fp32 buffers, one table-driven launch per kind of work (csrc/soap.hip; the host side is ultralytics/hip/soap.py).
+ * One table entry per TRAINABLE tensor (a frozen tensor has none), in device memory.  Entries hold offsets, not pointers: the gradient
+ * base differs between the step's gradient buffer and the accumulation buffer.  All Gram matrices of the model live in one pool and
+ * all eigenbases in another of the same layout, grouped by matrix size n so that the n x n matrices form one (count_n, n, n) tensor.
+ * The *_blk columns give the first workgroup of the entry in each launch (the host sums the tile counts); a workgroup finds its entry
+ * by binary search, so no launch count depends on the number of tensors. */
+#define DY_SOAP_MAX_DIMS 5
+typedef struct DySoapDesc {
+  long off;                         /* first element in the flat parameter layout (params, grads, m, v, scratch) */
+  long numel;
+  long pool_off[DY_SOAP_MAX_DIMS];  /* per dimension: first float of its n x n Gram matrix / eigenbasis in the pools */
+  int group;                        /* optimizer group 0 bias, 1 decayed weights, 2 norm weights */
+  int ndim;                         /* 1..DY_SOAP_MAX_DIMS */
+  int shape[DY_SOAP_MAX_DIMS];      /* unused dimensions 1 */
+  int has_q[DY_SOAP_MAX_DIMS];      /* 1: the dimension keeps a Gram matrix and a basis; 0: none (a 1-D tensor, a dimension above
+                                       max_precond_dim): it passes through every rotation */
+  int ord_off[DY_SOAP_MAX_DIMS];    /* per dimension: first int of its order vector (n ints) in the order pool of a QR refresh */
+  int rot_blk[DY_SOAP_MAX_DIMS];    /* first workgroup in dimension k's dy_soap_rotate launch: 32 x 32 output tiles,
+                                       ceil(n / 32) * ceil(numel / n / 32) of them, or ceil(numel / 1024) where it passes through */
+  int gram_blk[DY_SOAP_MAX_DIMS];   /* first workgroup of (entry, k) in the dy_soap_gram launch: 1 where n <= 8, else ceil(n / 32)^2;
+                                       a dimension without a Gram matrix takes none */
+  int ew_blk;                       /* first workgroup in the element-wise launches: ceil(numel / 1024) each */
+  int reserved;
+} DySoapDesc;
+int dy_soap_desc_bytes(void); /* sizeof(DySoapDesc) in the library (bindings check their layout) */
+/* The first two launches of dy_optimizer_step on their own (GradScaler.unscale_ + clip_grad_norm_, engine/trainer.py:949-953):
+ * state[2] found_inf, state[3] the unscaled norm, state[4] the clip coefficient.  Every SOAP entry below reads found_inf on the device
+ * and leaves its outputs untouched when it is set; the unscale x clip factor is (1 / state[0]) * state[4]. */
+int dy_grad_norm(const float* grads, long n, const float* hyper, float* state, float* partials, hipStream_t stream);
+/* SOAP.project / project_back (engine/trainer.py:283-309, :352-378) for dimension `dim` of every tensor: viewed as (A, n, B) around
+ * it, dst[a, j, b] = sum_i src[a, i, b] * Q[i, j] (back: Q[j, i]); a tensor without a basis there is copied.  Applied for dim = 0 ..
+ * max ndim - 1 this is the reference's chain of tensordots (only the summation order inside a dot product differs).  scaled: src is
+ * the raw gradient, multiplied by the unscale x clip factor as it is read.  dst != src. */
+int dy_soap_rotate(float* dst, const float* src, const DySoapDesc* table, int n_tensors, int n_blocks, const float* basis, int dim,
+                   int back, int scaled, const float* state, hipStream_t stream);
+/* SOAP.update_preconditioner's Gram update (engine/trainer.py:311-350, the lerp_ of :320-341): GG <- GG + (1 - beta2) *
+ * (G_(k) G_(k)^T - GG) for every (tensor, dimension) that keeps one, G_(k) the mode-k unfolding of the unscaled, clipped gradient.
+ * Each output tile is summed by one workgroup in a fixed order. */
+int dy_soap_gram(float* gram, const float* grads, const DySoapDesc* table, int n_tensors, int n_blocks, float one_minus_beta2,
+                 const float* state, hipStream_t stream);
+/* SOAP.step's moments in the eigenbasis (engine/trainer.py:152-255, :210-213): m <- beta1 m + (1 - beta1) gp, v <- beta2 v +
+ * (1 - beta2) gp^2, upd = m / (sqrt(v) + eps) over every table entry; gp and upd may be the same buffer. */
+int dy_soap_adam(float* m, float* v, const float* gp, float* upd, const DySoapDesc* table, int n_tensors, int n_blocks, float beta1,
+                 float one_minus_beta1, float beta2, float one_minus_beta2, float eps, const float* state, hipStream_t stream);
+/* ... and its parameter update (:221-247): p <- p - size3[group] * upd, then p <- p - decay3[group] * p where decay3[group] > 0
+ * (decay = lr * weight_decay).  size3 / decay3: three HOST floats each, copied at enqueue time (kernel arguments, as dy_set_hyper). */
+int dy_soap_apply(float* params, const float* upd, const DySoapDesc* table, int n_tensors, int n_blocks, const float* size3,
+                  const float* decay3, const float* state, hipStream_t stream);
+/* get_orthogonal_matrix_QR's exp_avg_sq.index_select(dim, sort_idx) (engine/trainer.py:416-473, :457) for dimension `dim` of every
+ * tensor: dst[a, j, b] = src[a, order[j], b]; a tensor without a basis there is copied.  dst != src. */
+int dy_soap_permute_v(float* dst, const float* src, const DySoapDesc* table, int n_tensors, int n_blocks, const int* order, int dim,
+                      const float* state, hipStream_t stream);
+
 /* ---- validation: the per-batch half of DetectionValidator.update_metrics in ONE launch --
  *      _prepare_batch/_prepare_pred (models/yolo/detect/val.py:93-115: xywh2xyxy * imgsz, scale_boxes + clip_boxes),
  *      box_iou (utils/metrics.py:53-73) and BaseValidator.match_predictions (engine/validator.py:217-257, numpy path).
