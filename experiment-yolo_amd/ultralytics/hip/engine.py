@@ -14,6 +14,8 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+from collections import namedtuple
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -69,11 +71,6 @@ PLANAR_CV1 = os.environ.get("DY_PLANAR_CV1", "1") != "0"
 # behind the concatenation reads pixel (y >> 1, x >> 1) of the low-resolution tensor where it stages that member (UpAct; DySegs.acc = 2).
 # DY_UPSEG=0: dy_upsample2x writes the four-times-larger copy.
 UPSEG = os.environ.get("DY_UPSEG", "1") != "0"
-# Weight gradients of SMALL maps (N*H*W <= DY_SIDE_SMALL pixels) on the side stream beside the input-gradient chain: there a launch is
-# mostly fixed latency and leaves CUs idle (profiles/r04_stage_ab.md), so the layer gives up the BatchNorm-in-the-weight-gradient fusion
-# (a separate backward-apply launch writes d(raw)) to take its weight gradient off the critical path.  0 (default): off -- MEASURED
-# SLOWER (round 4, one box): 11.33 ms off, 11.66 for maps <= 40x40, 11.99 <= 80x80, 12.17 <= 160x160 (profiles/r04_stage_ab.md).
-SIDE_SMALL = int(os.environ.get("DY_SIDE_SMALL", "0"))
 # ... in training too: forward and weight gradient read the low-resolution tensor, the input gradient of that member goes to a
 # full-resolution gradient tensor that Upsample's backward folds as before.  DY_UPSEG_TRAIN=0: training runs the up-sampling launch.
 UPSEG_TRAIN = UPSEG and os.environ.get("DY_UPSEG_TRAIN", "1") != "0"
@@ -134,6 +131,82 @@ def dev_empty(shape, dtype, device):
     if POISON and t.numel():
         t.view(-1).view(torch.uint8).fill_(0xFF)
     return t
+
+
+# ---- the backward of one Conv + BatchNorm + activation: WHICH launches make it up is decided here and nowhere else ----
+RED_DONE, RED_ROWS, RED_ACC, RED_3L, RED_3L_ANY = "done", "rows", "acc", "three-launch", "three-launch any-width"  # the BatchNorm sums
+RES_NONE, RES_RIDE, RES_ADD, RES_COPY = "none", "rides the reduce", "dy_add", "dy_copy_slice"                       # the shortcut's gradient
+BWD_NONE, BWD_DGRAD_ONLY, BWD_FUSED, BWD_WGRAD_BN, BWD_APPLY = "nothing", "dgrad only", "wgrad + dgrad", "wgrad with BN, dgrad", "apply, wgrad / dgrad"
+DRAW_NONE, DRAW_SHARED, DRAW_OWN = "stays in LDS", "shared scratch", "own buffer"                                   # where d(raw) lives
+ConvBwdForm = namedtuple("ConvBwdForm", "reduce shortcut launch draw wgrad")  # RED_*, RES_*, BWD_*, DRAW_*, holds a weight-gradient launch
+# what a weight-gradient kernel with the BatchNorm backward inside takes besides the convolution's operands (draw None: d(raw) stays in LDS)
+BnBwd = namedtuple("BnBwd", "raw draw coef acc_b gbn_w gbn_b count")
+
+
+class ConvBwdFacts(NamedTuple):
+    """What ``conv_bwd_form`` decides from: plain values (``Engine._bwd_facts`` gathers them, a host test enumerates them)."""
+    trainable: bool   # False: every parameter of the layer is frozen
+    acc: bool         # accumulator statistics present (spec.acc_b)
+    act: int
+    k1s1: bool        # 1x1, stride 1
+    ld: bool          # LDConv's column form
+    whole_in: bool    # cin / cout are whole 8-channel granules
+    whole_out: bool
+    raw_dense: bool   # raw.ld == cout
+    x_kind: str       # the input: "plain" (Act), "seg" (SegAct) or "other"
+    x_grad: bool      # ... needs a gradient
+    planes: bool      # the output (and so dY) in two planes
+    branch: bool      # recording off the main stream (cur_sid)
+    side_wgrad: bool
+    deferred: bool    # a deferred list present: the batched reduction finishes the weight gradients
+    fused_ok: bool    # dy_conv1x1_wgrad_dgrad_supported / dy_conv1x1_dgrad_bn_supported for this geometry (host functions, no launch)
+    dgrad_ok: bool
+    reduced: bool = False    # the sums are there already: the group's reduce, or the epilogue of the dgrad that wrote dY (BN_DGRED)
+    rows: bool = False       # dY came from dy_conv1x1_rows_backward alone
+    res_grad: bool = False   # a shortcut that needs a gradient ...
+    res_same: bool = False   # ... as wide as the output ...
+    res_acc: bool = False    # ... which something wrote already
+
+
+def conv_bwd_form(f: ConvBwdFacts) -> ConvBwdForm:
+    """The form of one Conv + BatchNorm + activation backward.  Mutates nothing; the switches are read as they are NOW."""
+    acc, silu = BN_ACC and f.acc, f.act == DY_ACT_SILU
+    if not f.res_grad:
+        shortcut = RES_NONE
+    elif acc and BN_RES and f.res_same and not f.reduced:
+        shortcut = RES_RIDE
+    else:
+        shortcut = RES_ADD if f.res_acc else RES_COPY
+    if not acc:
+        reduce = RED_3L if f.whole_out else RED_3L_ANY
+    elif f.reduced:
+        reduce = RED_DONE
+    else:  # (rows: zero outside the loss's foreground anchors, and so are the summands)
+        reduce = RED_ROWS if f.rows and shortcut != RES_RIDE else RED_ACC
+    # the one-launch kernels (BNF 5 / 7 and 13 / 15 of csrc/conv_wgrad.hip) keep d(raw) in LDS: 1x1, whole granules, an input that takes a
+    # gradient (a concatenation with members that need none takes them too: their pieces go to a sink, _segs)
+    one = f.k1s1 and not f.ld and f.x_kind != "other" and f.x_grad and f.whole_in and f.whole_out
+    # BatchNorm backward inside the weight-gradient kernel; a frozen layer in two planes keeps these launches where the dgrad-only
+    # kernel does not take it (its parameter gradients land in the sinks)
+    in_wgrad = bool(acc and BN_WGRAD and silu and not f.side_wgrad and f.raw_dense and (f.trainable or f.planes))
+    if not f.trainable and not f.planes and not f.x_grad:
+        launch = BWD_NONE  # (only the shortcut carried a gradient on)
+    elif not f.trainable and FROZEN_DGRAD and acc and silu and one and f.dgrad_ok:
+        launch = BWD_DGRAD_ONLY  # no shared scratch: branch and side-stream backward passes may take it too
+    elif in_wgrad and WGRAD_DGRAD and one and not f.branch and f.fused_ok:
+        launch = BWD_FUSED
+    else:
+        launch = BWD_WGRAD_BN if in_wgrad else BWD_APPLY
+    # the weight gradient reads d(raw) on the side stream while the main stream moves on to the next layer (or this layer's
+    # backward runs on a branch beside the main chain's): then it cannot be the shared scratch
+    draw = DRAW_NONE if launch in (BWD_NONE, BWD_DGRAD_ONLY, BWD_FUSED) else DRAW_OWN if (f.side_wgrad and f.deferred) or f.branch else DRAW_SHARED
+    return ConvBwdForm(reduce, shortcut, launch, draw, launch in (BWD_FUSED, BWD_WGRAD_BN) or (launch == BWD_APPLY and f.trainable))
+
+
+def conv_bwd_reads_parts(f: ConvBwdFacts) -> bool:
+    """Asked at FORWARD time (Engine.seg_conv_ok / planes_ok): as a trainable layer, the backward will take a form that reads a
+    segmented input and a two-plane dY -- the weight-gradient kernels with the BatchNorm backward inside."""
+    return conv_bwd_form(f._replace(trainable=True)).launch in (BWD_FUSED, BWD_WGRAD_BN)
 
 
 class Arena:
@@ -240,9 +313,8 @@ class Act:
     def _gbuf(self):
         st = self.st
         if st.gbuf is None:
-            st.gbuf = (st.eng.transient(tuple(st.buf.shape), st.buf.dtype) if st.buf is not None
-                       else st.eng.transient((st.N, st.H, st.W, st.C), torch.float16))
-            st.eng.hold(st.gbuf)
+            st.gbuf = (st.eng.held(tuple(st.buf.shape), st.buf.dtype) if st.buf is not None
+                       else st.eng.held((st.N, st.H, st.W, st.C), torch.float16))
         return st.gbuf
 
     @property
@@ -447,7 +519,6 @@ class Engine:
 
     # ---- two-stream plumbing: fork = "side waits for everything issued on main so far", join = "main waits for side" ----
     side_wgrad = False      # StepPlan switches it on for its backward trace
-    _side_used = False      # a weight gradient of this backward pass went to the side stream (SIDE_SMALL): flush_wgrad joins
     cur_sid = 0             # stream id launches go to (0 = the caller's current stream); set by ``branch`` / ``_on``
     _side_streams = None
     _FORK, _JOIN = "<fork>", "<join>"
@@ -653,6 +724,12 @@ class Engine:
             return self.arena.take(tuple(shape), dtype)
         return dev_empty(tuple(shape), dtype, self.device)
 
+    def held(self, shape, dtype):
+        """A transient buffer that recorded launches keep alive."""
+        t = self.transient(shape, dtype)
+        self.hold(t)
+        return t
+
     def new_storage(self, N, H, W, C, dtype=torch.float16):
         st = Storage(self, N, H, W, C, dtype)
         self.hold(st.buf)
@@ -810,10 +887,22 @@ class Engine:
         if not (PLANAR and isinstance(x, SegAct) and spec.ks == 1 and spec.stride == 1 and spec.ld is None and len(x.parts) <= 8
                 and x.C == spec.cin_phys and all(q.st.buf.dtype == torch.float16 for q in x.parts)):
             return False
-        if self.tape is not None and not (self.training and BN_ACC and BN_WGRAD and spec.acc_b is not None and spec.act == DY_ACT_SILU
-                                          and not self.side_wgrad and spec.bn is not None):
+        if self.tape is not None and not (self.training and conv_bwd_reads_parts(self._bwd_facts(spec, x))):
             return False
         return bool(self.L.dy_conv1x1_segs_supported(x.C, spec.cout, C.byref(self._segs(x))))
+
+    def _bwd_facts(self, spec, x, planes=False, raw_dense=True, **dataflow):
+        """The facts ``conv_bwd_form`` decides from, as they stand now (the forward predicates ask ahead of the backward pass: a raw
+        output of whole granules is dense, and the facts that differ by then -- a deferred list -- do not bear on what they ask)."""
+        kind = "seg" if isinstance(x, SegAct) else "plain" if isinstance(x, Act) else "other"
+        k1s1 = spec.ks == 1 and spec.stride == 1
+        geom = (x.N, x.H, x.W, spec.cin, spec.cout) if (k1s1 and spec.ld is None and kind != "other") else None
+        return ConvBwdFacts(trainable=spec.trainable, acc=spec.acc_b is not None, act=spec.act, k1s1=k1s1, ld=spec.ld is not None,
+                            whole_in=spec.cin == spec.cin_phys, whole_out=spec.cout == spec.cout_phys, raw_dense=raw_dense, x_kind=kind,
+                            x_grad=bool(x.needs_grad), planes=planes, branch=bool(self.cur_sid), side_wgrad=bool(self.side_wgrad),
+                            deferred=self.deferred_wgrad is not None,
+                            fused_ok=geom is not None and bool(self.L.dy_conv1x1_wgrad_dgrad_supported(*geom)),
+                            dgrad_ok=geom is not None and bool(self.L.dy_conv1x1_dgrad_bn_supported(*geom)), **dataflow)
 
     def snapshot(self, x):
         """``x`` as one tensor for INSPECTION (a per-layer capture): a copy that never joins the backward pass -- a copy made by
@@ -829,9 +918,8 @@ class Engine:
     def planes_ok(self, spec, x):
         """``spec`` (a 1x1 Conv + BatchNorm + SiLU) may write its output as two planes: the training forms that take them are the
         accumulator-statistics apply, the split backward reduce and the BatchNorm-in-the-weight-gradient kernel."""
-        if not (PLANAR and PLANAR_CV1 and self.training and BN_ACC and BN_WGRAD and spec.acc_f is not None and spec.acc_b is not None
-                and spec.ks == 1 and spec.stride == 1 and spec.ld is None and spec.act == DY_ACT_SILU and spec.bn is not None
-                and not self.side_wgrad and spec.cout % 16 == 0):
+        if not (PLANAR and PLANAR_CV1 and self.training and spec.acc_f is not None and spec.ks == 1 and spec.stride == 1 and spec.ld is None
+                and spec.cout % 16 == 0 and conv_bwd_reads_parts(self._bwd_facts(spec, x, planes=True))):
             return False
         return not isinstance(x, SegAct) or self.seg_conv_ok(spec, x)
 
@@ -840,8 +928,7 @@ class Engine:
         buf = self.transient((2, N, H, W, c), torch.float16)
         sts = [Storage.over(self, buf[0]), Storage.over(self, buf[1])]
         if self.tape is not None:
-            g = self.transient((2, N, H, W, c), torch.float16)
-            self.hold(g)
+            g = self.held((2, N, H, W, c), torch.float16)
             sts[0].gbuf, sts[1].gbuf = g[0], g[1]
         self.hold(buf)
         return sts[0].act(), sts[1].act()
@@ -865,19 +952,27 @@ class Engine:
         self.call("dy_conv_forward", x.ptr, x.ld, spec.wpack.data_ptr(), _ptr(bias), y_ptr, ldy, partials_ptr, x.N, x.H, x.W,
                   x.Cp, spec.cout if cout is None else cout, spec.ks, spec.stride, 1, 0, 0, epi, None)
 
-    def _partials(self, nbytes):
-        """Partial-sum rows of the three-launch BatchNorm form: the shared scratch on the main stream; a buffer of the launch's own while a
-        BRANCH is recorded (``cur_sid``: Detect's levels beside each other, DY_HEAD_STREAMS) -- the conv -> finalize pairs of several
-        branches would otherwise meet on one buffer.  (As ``draw`` in ``_conv_bn_act_bwd``.)"""
-        if not self.cur_sid:
-            return self.scratch("partials", nbytes)
-        t = self.transient((nbytes,), torch.uint8)
-        self.hold(t)
-        return t
+    def _staging(self, key, nbytes, own=None):
+        """Bytes one launch leaves for the next (partial-sum rows of the three-launch BatchNorm form, d(raw)): the shared scratch ``key`` on
+        the main stream; a buffer of the launch's own where ``own`` says so -- by default while a BRANCH is recorded (``cur_sid``: Detect's
+        levels beside each other, DY_HEAD_STREAMS): the conv -> finalize pairs of several branches would otherwise meet on one buffer."""
+        if not (self.cur_sid if own is None else own):
+            return self.scratch(key, nbytes)
+        return self.held((nbytes,), torch.uint8)
 
     def out_hw(self, spec, x):
         p = spec.ks // 2
         return (x.H + 2 * p - spec.ks) // spec.stride + 1, (x.W + 2 * p - spec.ks) // spec.stride + 1
+
+    @staticmethod
+    def _stem_hw(x):
+        """Output size of the stem (k 3, s 2, p 1) over the image batch ``x``."""
+        return (x.H - 1) // 2 + 1, (x.W - 1) // 2 + 1
+
+    @staticmethod
+    def _bn_ptrs(bn):
+        """The four BatchNorm parameter pointers in the order every apply / finalize / eval-coef entry takes them."""
+        return tuple(bn[k].data_ptr() for k in ("weight", "bias", "running_mean", "running_var"))
 
     def conv_bn_act(self, spec: ConvSpec, x: Act, out: Act | None = None, res: Act | None = None, defer_apply=False):
         """Conv.forward (reference nn/modules/conv.py:49-55) with training-mode BatchNorm; optional fused residual
@@ -891,13 +986,12 @@ class Engine:
                 return self._stem_direct(spec, x, out)
             if not self.training and self.tape is None and STEM_DIRECT and self._stem_eval_ok(spec, res):
                 # eval, un-fused: the raw conv from the image batch itself, then BatchNorm with running statistics as for any Conv
-                Ho, Wo = (x.H - 1) // 2 + 1, (x.W - 1) // 2 + 1
+                Ho, Wo = self._stem_hw(x)
                 raw = self.new_act(x.N, Ho, Wo, spec.cout)
                 y = out if out is not None else self.new_act(x.N, Ho, Wo, spec.cout)
                 bn = spec.bn
                 self.call("dy_stem_forward_eval", x.img.data_ptr(), spec.weight.data_ptr(), 0, raw.ptr, raw.ld, x.N, x.H, x.W, x.mul, 0)
-                self.call("dy_bn_eval_coef", bn["weight"].data_ptr(), bn["bias"].data_ptr(), bn["running_mean"].data_ptr(),
-                          bn["running_var"].data_ptr(), spec.coef.data_ptr(), spec.cout, spec.bn_eps)
+                self.call("dy_bn_eval_coef", *self._bn_ptrs(bn), spec.coef.data_ptr(), spec.cout, spec.bn_eps)
                 self.call("dy_bn_act_apply", raw.ptr, raw.ld, 0, 0, y.ptr, y.ld, spec.coef.data_ptr(), y.npix, spec.cout, spec.act)
                 return y
             x = x.materialize()
@@ -929,8 +1023,7 @@ class Engine:
             y0, y1 = y.parts
             self._conv_raw(spec, x, raw.ptr, raw.ld, DY_EPI_STATS | DY_EPI_STATS_ACC, self._acc_ready(spec.acc_f))
             self.call("dy_bn_act_apply_acc_split", raw.ptr, raw.ld, y0.ptr, y0.ld, y1.ptr, y1.ld, y0.C, spec.acc_f.data_ptr(),
-                      bn["weight"].data_ptr(), bn["bias"].data_ptr(), bn["running_mean"].data_ptr(), bn["running_var"].data_ptr(),
-                      spec.coef.data_ptr(), npix, spec.cout, spec.act, float(npix), spec.bn_eps, spec.bn_mom)
+                      *self._bn_ptrs(bn), spec.coef.data_ptr(), npix, spec.cout, spec.act, float(npix), spec.bn_eps, spec.bn_mom)
             self._record(live, y, lambda: self._conv_bn_act_bwd(spec, x, raw, y, None))
             return y
         if acc:
@@ -938,28 +1031,24 @@ class Engine:
             self._conv_raw(spec, x, raw.ptr, raw.ld, DY_EPI_STATS | DY_EPI_STATS_ACC, self._acc_ready(spec.acc_f))
             deferred = bool(defer_apply and res is None and spec.act == DY_ACT_SILU and self.tape is not None)
             self.call("dy_bn_act_apply_acc", raw.ptr, raw.ld, 0 if res is None else res.ptr, 0 if res is None else res.ld, y.ptr,
-                      y.ld, spec.acc_f.data_ptr(), bn["weight"].data_ptr(), bn["bias"].data_ptr(), bn["running_mean"].data_ptr(),
-                      bn["running_var"].data_ptr(), spec.coef.data_ptr(), 0 if deferred else npix, spec.cout, spec.act, float(npix),
-                      spec.bn_eps, spec.bn_mom)
+                      y.ld, spec.acc_f.data_ptr(), *self._bn_ptrs(bn), spec.coef.data_ptr(), 0 if deferred else npix, spec.cout, spec.act,
+                      float(npix), spec.bn_eps, spec.bn_mom)
             if deferred:
                 self._unapplied[(id(y.st), y.c0, y.C)] = (raw, spec)
         elif self.training:
             nparts = self.L.dy_conv_num_partials(x.N, x.H, x.W, spec.cin_phys, spec.cout, spec.ks, spec.stride, 1)
             cp16 = (spec.cout + 15) // 16 * 16  # the convolution's partial rows are round16(cout) floats wide
-            part = self._partials(nparts * 2 * cp16 * 4 + 4096)
+            part = self._staging("partials", nparts * 2 * cp16 * 4 + 4096)
             self._conv_raw(spec, x, raw.ptr, raw.ld, DY_EPI_STATS, part.data_ptr())
             if cp16 == spec.cout:
-                self.call("dy_bn_finalize", part.data_ptr(), nparts, 1.0, 0, 0, 0.0, 0, 0, 0.0, bn["weight"].data_ptr(),
-                          bn["bias"].data_ptr(), bn["running_mean"].data_ptr(), bn["running_var"].data_ptr(),
+                self.call("dy_bn_finalize", part.data_ptr(), nparts, 1.0, 0, 0, 0.0, 0, 0, 0.0, *self._bn_ptrs(bn),
                           spec.coef.data_ptr(), spec.cout, float(npix), spec.bn_eps, spec.bn_mom, 1)
             else:
-                self.call("dy_bn_finalize_ld", part.data_ptr(), nparts, cp16, bn["weight"].data_ptr(), bn["bias"].data_ptr(),
-                          bn["running_mean"].data_ptr(), bn["running_var"].data_ptr(), spec.coef.data_ptr(), spec.cout, float(npix),
+                self.call("dy_bn_finalize_ld", part.data_ptr(), nparts, cp16, *self._bn_ptrs(bn), spec.coef.data_ptr(), spec.cout, float(npix),
                           spec.bn_eps, spec.bn_mom, 1, _ptr(bn.get("nbt")))
         else:
             self._conv_raw(spec, x, raw.ptr, raw.ld, 0)
-            self.call("dy_bn_eval_coef", bn["weight"].data_ptr(), bn["bias"].data_ptr(), bn["running_mean"].data_ptr(),
-                      bn["running_var"].data_ptr(), spec.coef.data_ptr(), spec.cout, spec.bn_eps)
+            self.call("dy_bn_eval_coef", *self._bn_ptrs(bn), spec.coef.data_ptr(), spec.cout, spec.bn_eps)
         if not acc:
             # ragged: the raw buffer's pad lanes were never written (the convolution masks its stores per channel); the apply drops
             # them and writes zeros into y's
@@ -975,15 +1064,14 @@ class Engine:
     def _stem_direct(self, spec, x: ImageAct, out=None):
         """model.0 from the image batch itself (csrc/stem.hip): forward conv + statistics, the usual apply; backward = the usual
         reduce, then the weight gradient with the BatchNorm / SiLU backward apply inside (no input gradient exists)."""
-        Ho, Wo = (x.H - 1) // 2 + 1, (x.W - 1) // 2 + 1
+        Ho, Wo = self._stem_hw(x)
         bn = spec.bn
         raw = self.new_act(x.N, Ho, Wo, spec.cout)
         y = out if out is not None else self.new_act(x.N, Ho, Wo, spec.cout)
         npix = x.N * Ho * Wo
         self.call("dy_stem_forward", x.img.data_ptr(), spec.weight.data_ptr(), raw.ptr, raw.ld, self._acc_ready(spec.acc_f), x.N, x.H, x.W, x.mul)
-        self.call("dy_bn_act_apply_acc", raw.ptr, raw.ld, 0, 0, y.ptr, y.ld, spec.acc_f.data_ptr(), bn["weight"].data_ptr(),
-                  bn["bias"].data_ptr(), bn["running_mean"].data_ptr(), bn["running_var"].data_ptr(), spec.coef.data_ptr(), npix, spec.cout,
-                  spec.act, float(npix), spec.bn_eps, spec.bn_mom)
+        self.call("dy_bn_act_apply_acc", raw.ptr, raw.ld, 0, 0, y.ptr, y.ld, spec.acc_f.data_ptr(), *self._bn_ptrs(bn), spec.coef.data_ptr(), npix,
+                  spec.cout, spec.act, float(npix), spec.bn_eps, spec.bn_mom)
         if self.tape is not None and not spec.trainable:  # a frozen stem has no backward at all: no input gradient exists either
             self._no_grad(y)
         elif self.tape is not None:
@@ -994,13 +1082,10 @@ class Engine:
                 ns = self.L.dy_stem_grid(x.N, x.H, x.W)
                 se = 9 * 16 * 16
                 deferred = self.deferred_wgrad is not None
-                slabs = self.transient((ns * se,), torch.float32) if deferred else self.scratch("slabs", ns * se * 4)
-                self.hold(slabs)
+                slabs = self._deferred_slabs(spec, ns * se, ns) if deferred else self.scratch("slabs", ns * se * 4)
                 self.call("dy_stem_wgrad_bn", x.img.data_ptr(), y.gptr, y.ld, raw.ptr, raw.ld, spec.coef.data_ptr(), spec.acc_b.data_ptr(),
                           spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(), float(npix), slabs.data_ptr(), x.N, x.H, x.W, x.mul)
-                if deferred:
-                    self.deferred_wgrad.append((spec, slabs, ns))
-                else:  # reduce now (one descriptor through the batched entry)
+                if not deferred:  # reduce now (one descriptor through the batched entry)
                     keep, self.deferred_wgrad = self.deferred_wgrad, [(spec, slabs, ns)]
                     self.flush_wgrad()
                     self.deferred_wgrad = keep
@@ -1033,9 +1118,8 @@ class Engine:
         npx = [y.npix for _, _, _, y, _ in outs]
         self.call("dy_bn_act_apply_acc_group", len(outs), self._arr(P, [raw.ptr for _, _, raw, _, _ in outs]), self._arr(I, [raw.ld for _, _, raw, _, _ in outs]),
                   self._arr(P, [y.ptr for _, _, _, y, _ in outs]), self._arr(I, [y.ld for _, _, _, y, _ in outs]),
-                  self._arr(P, [sp.acc_f.data_ptr() for sp, *_ in outs]), self._arr(P, [b["weight"].data_ptr() for b in bn]),
-                  self._arr(P, [b["bias"].data_ptr() for b in bn]), self._arr(P, [b["running_mean"].data_ptr() for b in bn]),
-                  self._arr(P, [b["running_var"].data_ptr() for b in bn]), self._arr(P, [sp.coef.data_ptr() for sp, *_ in outs]),
+                  self._arr(P, [sp.acc_f.data_ptr() for sp, *_ in outs]), *[self._arr(P, col) for col in zip(*map(self._bn_ptrs, bn))],
+                  self._arr(P, [sp.coef.data_ptr() for sp, *_ in outs]),
                   self._arr(Lg, [0 if d else n for n, (*_, d) in zip(npx, outs)]), self._arr(I, [sp.cout for sp, *_ in outs]),
                   self._arr(F, [float(n) for n in npx]), self._arr(F, [sp.bn_eps for sp, *_ in outs]), self._arr(F, [sp.bn_mom for sp, *_ in outs]))
         for spec, x, raw, y, d in outs:
@@ -1069,207 +1153,143 @@ class Engine:
         return [y for _, _, _, y, _ in outs]
 
     def _conv_bn_act_bwd(self, spec, x, raw, y, res, reduced=False):
-        if isinstance(y, SegAct):  # two output planes (conv_bn_act): the split reduce, then the weight gradient with dY in planes
-            y0, y1 = y.parts
-            assert y0.grad_ready() and y1.grad_ready(), f"gradient of {spec.name} output incomplete"
+        """Gather the facts, ask ``conv_bwd_form``, issue the launches of the form it returns."""
+        planes = isinstance(y, SegAct)  # two output planes (conv_bn_act): dY is (y0, y1), split at channel y0.C
+        y0, y1 = y.parts if planes else (y, None)
+        assert y0.grad_ready() and (y1 is None or y1.grad_ready()), f"gradient of {spec.name} output incomplete"
+        if planes:
             assert y1.gptr - y0.gptr == y0.npix * y0.ld * 2 and y0.ld == y1.ld == y0.C, "the planes' gradients are not one allocation"
-            npix = y0.npix
-            self.call("dy_bn_act_bwd_reduce_acc_split", y0.gptr, y0.ld, y1.gptr, y1.ld, y0.C, raw.ptr, raw.ld, spec.coef.data_ptr(),
-                      self._acc_ready(spec.acc_b), npix, spec.cout, spec.act)
-            if not spec.trainable and self._dgrad_only_ok(spec, x):  # frozen: the input gradient alone, from the two planes of dY
-                self._dgrad_only(spec, x, raw, y0.gptr, y0.ld, npix, planes=(y1.gptr, y0.C))
-                return
-            # (a frozen layer in planes without that kernel keeps the trainable launches: its parameter gradients land in the sinks)
-            if self._wgrad_dgrad_ok(spec, x):
-                draw = None  # the fused launch keeps d(raw) in LDS
-            elif self.cur_sid:
-                draw = self.transient((npix * spec.cout,), torch.float16)
-                self.hold(draw)
-            else:
-                draw = self.scratch("draw", npix * spec.cout * 2)
-            bn = (raw, draw, spec.coef.data_ptr(), spec.acc_b.data_ptr(), spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(), float(npix))
-            self._conv_bwd(spec, x, y0.gptr, y0.ld, y0.H, y0.W, bn=bn, planes=(y1.gptr, y0.C))
-            return
-        assert y.grad_ready(), f"gradient of {spec.name} output incomplete"
-        npix = y.npix
-        acc = BN_ACC and spec.acc_b is not None
+        npix = y0.npix
+        ykey = (id(y0.st), y0.c0, y0.C)  # (a plane is neither a dgrad's sole product nor a rows gradient: both look-ups miss)
         fused_red = id(spec) in self._reduced  # the dgrad that wrote y's gradient already summed g and g*xhat into acc_b
-        if fused_red and self._gw.get((id(y.st), y.c0, y.C)) != 1:
+        if fused_red and self._gw.get(ykey) != 1:
             raise RuntimeError(f"{spec.name}: BatchNorm backward reduce was fused into a dgrad that is not the only writer of the gradient")
-        rg = (0, 0, 0)
-        if res is not None and res.needs_grad:
-            racc = res.grad_target()
-            if acc and BN_RES and res.C == spec.cout and not fused_red:  # the shortcut's gradient (= dy) rides on the reduce pass below
-                rg = (res.gptr, res.ld, racc)
-            elif racc:
-                self.call("dy_add", res.gptr, res.ld, y.gptr, y.ld, 0, 0, res.gptr, res.ld, npix, res.C)
-            else:
-                self.call("dy_copy_slice", y.gptr, y.ld, res.gptr, res.ld, npix, res.C)
-        ykey = (id(y.st), y.c0, y.C)
-        rows = self._rows_grad.get(ykey)
-        if rows is not None and self._gw.get(ykey) != 1:
-            rows = None  # somebody else wrote into that gradient as well: it is dense
-        if acc and (fused_red or reduced):  # reduced: conv_bn_act_group ran this layer's reduce with its group's
-            pass
-        elif acc and rows is not None and rg == (0, 0, 0):
-            # y's gradient came from dy_conv1x1_rows_backward alone: zero outside the loss's foreground anchors, so are the summands
+        res_grad = res is not None and res.needs_grad
+        racc = res.grad_target() if res_grad else 0
+        rows = self._rows_grad.get(ykey) if self._gw.get(ykey) == 1 else None  # (somebody else wrote into that gradient as well: it is dense)
+        form = conv_bwd_form(self._bwd_facts(spec, x, planes, raw.ld == spec.cout, reduced=fused_red or reduced, rows=rows is not None,
+                                             res_grad=res_grad, res_same=res_grad and res.C == spec.cout, res_acc=bool(racc)))
+        coef = spec.coef.data_ptr()
+        stats = (spec.acc_b.data_ptr(), spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr()) if form.reduce in (RED_DONE, RED_ROWS, RED_ACC) else ()
+        rg = (res.gptr, res.ld, racc) if form.shortcut == RES_RIDE else (0, 0, 0)  # the shortcut's gradient (= dy) rides on the reduce pass below
+        if form.shortcut == RES_ADD:
+            self.call("dy_add", res.gptr, res.ld, y.gptr, y.ld, 0, 0, res.gptr, res.ld, npix, res.C)
+        elif form.shortcut == RES_COPY:
+            self.call("dy_copy_slice", y.gptr, y.ld, res.gptr, res.ld, npix, res.C)
+        if planes:
+            assert form.reduce == RED_ACC and form.launch != BWD_APPLY, f"{spec.name}: two planes need the BatchNorm-in-the-weight-gradient path"
+            self.call("dy_bn_act_bwd_reduce_acc_split", y0.gptr, y0.ld, y1.gptr, y1.ld, y0.C, raw.ptr, raw.ld, coef, self._acc_ready(spec.acc_b),
+                      npix, spec.cout, spec.act)
+        elif form.reduce == RED_ROWS:
             asg, A, a0 = rows
-            self.call("dy_bn_act_bwd_reduce_rows", y.gptr, y.ld, raw.ptr, raw.ld, spec.coef.data_ptr(), self._acc_ready(spec.acc_b),
-                      y.N, y.H * y.W, spec.cout, spec.act, asg, A, a0)
-        elif acc:
-            self.call("dy_bn_act_bwd_reduce_acc", y.gptr, y.ld, raw.ptr, raw.ld, spec.coef.data_ptr(), self._acc_ready(spec.acc_b),
-                      npix, spec.cout, spec.act, *rg)
-        elif spec.cout != spec.cout_phys:  # a ragged last granule: the any-width kernels (pad lanes of dy and raw dropped where read)
-            part = self._partials(2048 * 2 * spec.cout_phys * 4 + 4096)
+            self.call("dy_bn_act_bwd_reduce_rows", y.gptr, y.ld, raw.ptr, raw.ld, coef, self._acc_ready(spec.acc_b), y.N, y.H * y.W, spec.cout,
+                      spec.act, asg, A, a0)
+        elif form.reduce == RED_ACC:
+            self.call("dy_bn_act_bwd_reduce_acc", y.gptr, y.ld, raw.ptr, raw.ld, coef, self._acc_ready(spec.acc_b), npix, spec.cout, spec.act, *rg)
+        elif form.reduce != RED_DONE:
+            # (any-width: the pad lanes of dy and raw of a ragged last granule are dropped where they are read)
+            any_w = form.reduce == RED_3L_ANY
+            part = self._staging("partials", 2048 * 2 * spec.cout_phys * 4 + 4096)
             n = C.c_int(0)
-            self.call("dy_bn_act_bwd_reduce_c", y.gptr, y.ld, raw.ptr, raw.ld, spec.coef.data_ptr(), part.data_ptr(), 2048, npix,
-                      spec.cout, spec.act, C.byref(n))
-            self.call("dy_bn_bwd_finalize_ld", part.data_ptr(), n.value, spec.cout_phys, spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(),
-                      spec.bwdcoef.data_ptr(), spec.cout, float(npix), 0)
-        else:
-            part = self._partials(2048 * 2 * spec.cout * 4 + 4096)
-            n = C.c_int(0)
-            self.call("dy_bn_act_bwd_reduce", y.gptr, y.ld, raw.ptr, raw.ld, spec.coef.data_ptr(), part.data_ptr(), 2048, npix,
-                      spec.cout, spec.act, C.byref(n))
-            self.call("dy_bn_bwd_finalize", part.data_ptr(), n.value, spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(),
-                      spec.bwdcoef.data_ptr(), spec.cout, float(npix), 0)
-        frozen = not spec.trainable
-        if frozen:
-            # The BatchNorm backward sums above are still needed (batch statistics are live in a frozen layer, as in the reference); what
-            # follows is d(raw) and the input gradient only: no weight-gradient launch, no slabs, no reduce descriptor, and the
-            # gamma / beta sums of the two-launch form go to the sinks.
-            if not x.needs_grad:
-                return  # (only the shortcut carried a gradient on)
-            if acc and spec.act == DY_ACT_SILU and self._dgrad_only_ok(spec, x):
-                self._dgrad_only(spec, x, raw, y.gptr, y.ld, npix)
-                return
-        side_small = bool(not frozen and SIDE_SMALL and npix <= SIDE_SMALL and self.deferred_wgrad is not None and not self.cur_sid and not self.side_wgrad
-                          and acc and isinstance(x, Act) and x.needs_grad and spec.ld is None)
-        bn_wgrad = bool(not frozen and acc and BN_WGRAD and spec.act == DY_ACT_SILU and not self.side_wgrad and not side_small and raw.ld == spec.cout)
-        if bn_wgrad and self._wgrad_dgrad_ok(spec, x):
-            draw = None  # the fused launch keeps d(raw) in LDS
-        elif ((self.side_wgrad or side_small) and self.deferred_wgrad is not None) or self.cur_sid:
-            # the weight gradient reads this buffer on the side stream while the main stream moves on to the next layer (or this
-            # layer's backward runs on a branch beside the main chain's): it cannot be the shared scratch
-            draw = self.transient((npix * spec.cout_phys,), torch.float16)
-            self.hold(draw)
-        else:
-            draw = self.scratch("draw", npix * spec.cout_phys * 2)
-        if bn_wgrad:
-            # no apply launch: the weight-gradient kernel forms d(raw) while staging and leaves it in ``draw`` for the dgrad
-            bn = (raw, draw, spec.coef.data_ptr(), spec.acc_b.data_ptr(), spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(), float(npix))
-            self._conv_bwd(spec, x, y.gptr, y.ld, y.H, y.W, bn=bn)
+            self.call("dy_bn_act_bwd_reduce_c" if any_w else "dy_bn_act_bwd_reduce", y.gptr, y.ld, raw.ptr, raw.ld, coef, part.data_ptr(), 2048,
+                      npix, spec.cout, spec.act, C.byref(n))
+            self.call("dy_bn_bwd_finalize_ld" if any_w else "dy_bn_bwd_finalize", part.data_ptr(), n.value, *((spec.cout_phys,) if any_w else ()),
+                      spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(), spec.bwdcoef.data_ptr(), spec.cout, float(npix), 0)
+        # A frozen layer still needed the sums above (batch statistics are live in it, as in the reference); what follows for it is d(raw)
+        # and the input gradient only, and the gamma / beta sums of the apply launch go to the sinks.
+        pl = (y1.gptr, y0.C) if planes else None
+        if form.launch == BWD_DGRAD_ONLY:  # ONE launch that forms d(raw) and the input gradient and nothing else
+            dx, dxs = self._grad_dst(x)
+            self.call("dy_conv1x1_dgrad_bn", y0.gptr, pl[0] if pl else 0, y0.ld, pl[1] if pl else 0, raw.ptr, raw.ld, coef, stats[0], float(npix),
+                      spec.wpack_t.data_ptr(), *dx, dxs, x.N, x.H, x.W, spec.cin, spec.cout)
+        if form.launch in (BWD_NONE, BWD_DGRAD_ONLY):
             return
-        if acc:
-            self.call("dy_bn_act_bwd_apply_acc", y.gptr, y.ld, raw.ptr, raw.ld, draw.data_ptr(), spec.cout, spec.coef.data_ptr(),
-                      spec.acc_b.data_ptr(), spec.gbn_w.data_ptr(), spec.gbn_b.data_ptr(), npix, spec.cout, spec.act, float(npix))
+        draw = None if form.draw == DRAW_NONE else self._staging("draw", npix * spec.cout_phys * 2, own=form.draw == DRAW_OWN)
+        if form.launch != BWD_APPLY:
+            # no apply launch: the weight-gradient kernel forms d(raw) while staging and leaves it in ``draw`` for the dgrad (or in LDS)
+            self._conv_bwd(spec, x, y0.gptr, y0.ld, y0.H, y0.W, bn=BnBwd(raw, draw, coef, *stats, float(npix)), planes=pl, form=form.launch)
+            return
+        if stats:
+            self.call("dy_bn_act_bwd_apply_acc", y.gptr, y.ld, raw.ptr, raw.ld, draw.data_ptr(), spec.cout, coef, *stats, npix, spec.cout, spec.act,
+                      float(npix))
         else:  # (d(raw) lives at the physical width; a ragged last granule gets zeros in its pad lanes: the input gradient sums over them)
-            self.call("dy_bn_act_bwd_apply_c" if spec.cout != spec.cout_phys else "dy_bn_act_bwd_apply", y.gptr, y.ld, raw.ptr, raw.ld,
-                      draw.data_ptr(), spec.cout_phys, spec.coef.data_ptr(), spec.bwdcoef.data_ptr(), npix, spec.cout, spec.act, 0)
-        self._conv_bwd(spec, x, draw.data_ptr(), spec.cout_phys, y.H, y.W, side_hint=side_small, wgrad=not frozen)
+            self.call("dy_bn_act_bwd_apply_c" if form.reduce == RED_3L_ANY else "dy_bn_act_bwd_apply", y.gptr, y.ld, raw.ptr, raw.ld,
+                      draw.data_ptr(), spec.cout_phys, coef, spec.bwdcoef.data_ptr(), npix, spec.cout, spec.act, 0)
+        # (a frozen layer: the input gradient is all there is)
+        (self._conv_bwd if form.wgrad else self._input_grad)(spec, x, draw.data_ptr(), spec.cout_phys, y.H, y.W)
 
-    def _dgrad_only_ok(self, spec, x):
-        """The backward of the FROZEN ``spec`` (1x1 Conv + BatchNorm + SiLU, accumulator statistics) over ``x`` is ONE launch that forms
-        d(raw) and the input gradient and nothing else (dy_conv1x1_dgrad_bn).  It keeps d(raw) in LDS and uses no shared scratch, so
-        branch and side-stream backward passes may take it too."""
-        if not (FROZEN_DGRAD and BN_ACC and spec.bn is not None and spec.acc_b is not None and spec.act == DY_ACT_SILU and spec.ks == 1
-                and spec.stride == 1 and spec.ld is None and isinstance(x, (Act, SegAct)) and x.needs_grad
-                and spec.cout == spec.cout_phys and spec.cin == spec.cin_phys):
-            return False
-        return bool(self.L.dy_conv1x1_dgrad_bn_supported(x.N, x.H, x.W, spec.cin, spec.cout))
-
-    def _dgrad_only(self, spec, x, raw, dy_ptr, lddy, npix, planes=None):
+    def _grad_dst(self, x):
+        """Where a kernel writes the gradient of its input ``x`` -> ((pointer, ld, accumulate flag), segment table by reference or None).
+        A concatenation takes the table (every 8-channel piece goes to its member's gradient tensor, stored or added per member; a member
+        that needs none gets a sink: _segs) and (0, 0, 0); a tensor that needs no gradient a null pointer.  First writer stores."""
         if isinstance(x, SegAct):
             accs = [q.grad_target() if q.needs_grad else 0 for q in x.parts]
-            dxs, dx = C.byref(self._segs(x, grad=True, acc=accs)), (0, 0, 0)
-        else:
-            acc = x.grad_target()
-            dxs, dx = None, (x.gptr, x.ld, int(acc))
-        self.call("dy_conv1x1_dgrad_bn", dy_ptr, planes[0] if planes else 0, lddy, planes[1] if planes else 0, raw.ptr, raw.ld,
-                  spec.coef.data_ptr(), spec.acc_b.data_ptr(), float(npix), spec.wpack_t.data_ptr(), *dx, dxs, x.N, x.H, x.W, spec.cin, spec.cout)
+            return (0, 0, 0), C.byref(self._segs(x, grad=True, acc=accs))
+        if not x.needs_grad:
+            return (0, x.ld, 0), None
+        acc = x.grad_target()
+        return (x.gptr, x.ld, int(acc)), None
 
-    def _wgrad_dgrad_ok(self, spec, x):
-        """The backward of ``spec`` (a 1x1 Conv + BatchNorm + SiLU on the BatchNorm-in-the-weight-gradient path) over input ``x`` is ONE
-        launch: weight gradient and input gradient together (dy_conv1x1_wgrad_dgrad_*).  Side-stream and branch backward passes, LDConv
-        forms and inputs that need no gradient keep the two-launch list."""
-        if not (WGRAD_DGRAD and spec.ks == 1 and spec.stride == 1 and spec.ld is None and isinstance(x, (Act, SegAct)) and x.needs_grad
-                and not self.cur_sid and not self.side_wgrad and spec.cout == spec.cout_phys and spec.cin == spec.cin_phys):
-            return False
-        # (a concatenation with members that need no gradient -- their producers are frozen -- takes it too: their pieces go to a sink, _segs)
-        return bool(self.L.dy_conv1x1_wgrad_dgrad_supported(x.N, x.H, x.W, spec.cin, spec.cout))
+    def _deferred_slabs(self, spec, nfloats, ns, bias_acc=None):
+        """Slabs of ``spec``'s weight gradient that the batched reduction at the end of the backward pass finishes (``deferred_wgrad`` is
+        a list): a transient buffer, with its reduce descriptor's facts appended (``bias_acc``: the kernel also sums dY there)."""
+        slabs = self.held((nfloats,), torch.float32)
+        self.deferred_wgrad.append((spec, slabs, ns) if bias_acc is None else (spec, slabs, ns, bias_acc))
+        return slabs
 
-    def _conv_bwd(self, spec, x, dy_ptr, lddy, Ho, Wo, accumulate_w=0, defer=True, bn=None, bias_acc=None, planes=None, side_hint=False,
-                  wgrad=True):
-        """weight gradient + input gradient of one convolution given d(raw output) (fp16, (N,Ho,Wo,lddy)).
+    def _conv_bwd(self, spec, x, dy_ptr, lddy, Ho, Wo, accumulate_w=0, defer=True, bn=None, bias_acc=None, planes=None, form=None):
+        """weight gradient + input gradient of one convolution.  ``form`` BWD_APPLY: given d(raw output) (fp16, (N,Ho,Wo,lddy)); BWD_WGRAD_BN /
+        BWD_FUSED: given the gradient w.r.t. the ACTIVATED output and ``bn`` (a BnBwd); no form named: the two-launch one of what is handed.
         When the engine is collecting (``self.deferred_wgrad`` is a list: StepPlan's backward trace) the per-workgroup slabs of
         this layer are kept and reduced together with every other layer's by ONE ``dy_wgrad_reduce_batched`` launch at the end
         of the backward pass; weights shared by several calls (ScalSeq's conv3d: ``defer=False``) reduce immediately."""
-        if not wgrad:  # a frozen layer (dy_ptr = d(raw) from the apply launch): the input gradient is all there is
-            assert bn is None and bias_acc is None and planes is None
-            return self._input_grad(spec, x, dy_ptr, lddy, Ho, Wo)
+        if form is None:
+            form = BWD_APPLY if bn is None else BWD_WGRAD_BN
         ns, se = C.c_int(), C.c_long()
         self.L.dy_wgrad_workspace(x.N, x.H, x.W, spec.cin, spec.cout, spec.ks, spec.stride, C.byref(ns), C.byref(se))
         deferred = defer and not accumulate_w and self.deferred_wgrad is not None
         if self.wgrad_log is not None and not deferred:
             self.wgrad_log.append(spec)
         if deferred:
-            slabs = self.transient((ns.value * se.value,), torch.float32)
-            self.hold(slabs)
-            self.deferred_wgrad.append((spec, slabs, ns.value) if bias_acc is None else (spec, slabs, ns.value, bias_acc))
-            dw = 0
+            slabs, dw = self._deferred_slabs(spec, ns.value * se.value, ns.value, bias_acc), 0
         else:
-            slabs = self.scratch("slabs", ns.value * se.value * 4)
-            dw = spec.gweight.data_ptr()
+            slabs, dw = self.scratch("slabs", ns.value * se.value * 4), spec.gweight.data_ptr()
         # deferred weight gradients are off the critical path (needed only by the batched reduction at the end of the
         # backward pass): with ``side_wgrad`` they run on the side stream beside the input-gradient chain
-        side = deferred and (self.side_wgrad or side_hint)
+        side = deferred and self.side_wgrad
         if side:
-            self._side_used = True
             self.fork()
-        if bn is not None and bn[1] is None:  # fused (_wgrad_dgrad_ok): the input-gradient call's bookkeeping, then one launch for both
-            raw, _, coef, accb, gw, gb, cnt = bn
-            assert not side and self._wgrad_dgrad_ok(spec, x)
-            seg = isinstance(x, SegAct)
-            if seg:
-                accs = [q.grad_target() if q.needs_grad else 0 for q in x.parts]
-                dxs, dx = C.byref(self._segs(x, grad=True, acc=accs)), (0, 0, 0)
-            else:
-                acc = x.grad_target()
-                dxs, dx = None, (x.gptr, x.ld, int(acc))
-            tail = (x.N, x.H, x.W, spec.cin, spec.cout, accumulate_w)
+        seg = isinstance(x, SegAct)
+        geom = (x.N, x.H, x.W, spec.cin, spec.cout, accumulate_w)
+        if form != BWD_APPLY:
+            bn = BnBwd(*bn)
+            inner = (bn.coef, bn.acc_b, bn.gbn_w, bn.gbn_b, bn.count, slabs.data_ptr(), dw)
+            xs = (C.byref(self._segs(x)) if seg else None, 0 if seg else x.ptr, 0 if seg else x.ld)  # x a tensor or a concatenation (the planes forms)
+        if form == BWD_FUSED:  # the input-gradient call's bookkeeping, then one launch for both
+            assert not side
+            dx, dxs = self._grad_dst(x)
             wt = spec.wpack_t.data_ptr()
             if planes is not None:
-                self.call("dy_conv1x1_wgrad_dgrad_bn_planes", C.byref(self._segs(x)) if seg else None, 0 if seg else x.ptr, 0 if seg else x.ld,
-                          dy_ptr, planes[0], lddy, planes[1], raw.ptr, raw.ld, coef, accb, gw, gb, cnt, slabs.data_ptr(), dw, wt, *dx, dxs, *tail)
+                self.call("dy_conv1x1_wgrad_dgrad_bn_planes", *xs, dy_ptr, planes[0], lddy, planes[1], bn.raw.ptr, bn.raw.ld, *inner, wt, *dx, dxs, *geom)
             elif seg:
-                self.call("dy_conv1x1_wgrad_dgrad_bn_segs", C.byref(self._segs(x)), dy_ptr, lddy, raw.ptr, raw.ld, coef, accb, gw, gb, cnt,
-                          slabs.data_ptr(), dw, wt, dxs, *tail)
+                self.call("dy_conv1x1_wgrad_dgrad_bn_segs", xs[0], dy_ptr, lddy, bn.raw.ptr, bn.raw.ld, *inner, wt, dxs, *geom)
             else:
-                self.call("dy_conv1x1_wgrad_dgrad_bn", x.ptr, x.ld, dy_ptr, lddy, raw.ptr, raw.ld, coef, accb, gw, gb, cnt, slabs.data_ptr(), dw,
-                          wt, *dx, *tail)
+                self.call("dy_conv1x1_wgrad_dgrad_bn", x.ptr, x.ld, dy_ptr, lddy, bn.raw.ptr, bn.raw.ld, *inner, wt, *dx, *geom)
             return
-        if planes is not None:  # dY in two planes (dy_ptr, planes[0]), split at channel planes[1]; x a tensor or a concatenation
-            raw, draw, coef, accb, gw, gb, cnt = bn
-            seg = isinstance(x, SegAct)
-            self.call("dy_conv1x1_wgrad_bn_planes", C.byref(self._segs(x)) if seg else None, 0 if seg else x.ptr, 0 if seg else x.ld, dy_ptr,
-                      planes[0], lddy, planes[1], raw.ptr, raw.ld, draw.data_ptr() if x.needs_grad else 0, coef, accb, gw, gb, cnt,
-                      slabs.data_ptr(), dw, x.N, x.H, x.W, spec.cin, spec.cout, accumulate_w)
-            dy_ptr, lddy = draw.data_ptr(), spec.cout
-        elif bn is not None and isinstance(x, SegAct):  # (seg_conv_ok checked at forward time that this path is the one taken)
-            raw, draw, coef, accb, gw, gb, cnt = bn
-            self.call("dy_conv1x1_wgrad_bn_segs", C.byref(self._segs(x)), dy_ptr, lddy, raw.ptr, raw.ld, draw.data_ptr() if x.needs_grad else 0,
-                      coef, accb, gw, gb, cnt, slabs.data_ptr(), dw, x.N, x.H, x.W, spec.cin, spec.cout, accumulate_w)
-            dy_ptr, lddy = draw.data_ptr(), spec.cout
-        elif bn is not None:  # dy_ptr is the gradient w.r.t. the ACTIVATED output: BatchNorm + SiLU backward inside the kernel
-            raw, draw, coef, accb, gw, gb, cnt = bn
-            head = (x.ptr, x.ld, dy_ptr, lddy, raw.ptr, raw.ld, draw.data_ptr() if x.needs_grad else 0, coef, accb, gw, gb, cnt,
-                    slabs.data_ptr(), dw, x.N, x.H, x.W)
-            if spec.ld is not None:
+        if form == BWD_WGRAD_BN:  # the kernel leaves d(raw) in ``bn.draw`` for the input gradient (where one is needed)
+            dr = bn.draw.data_ptr() if x.needs_grad else 0
+            if planes is not None:  # dY in two planes (dy_ptr, planes[0]), split at channel planes[1]
+                self.call("dy_conv1x1_wgrad_bn_planes", *xs, dy_ptr, planes[0], lddy, planes[1], bn.raw.ptr, bn.raw.ld, dr, *inner, *geom)
+            elif seg:  # (seg_conv_ok checked at forward time that this path is the one taken)
+                self.call("dy_conv1x1_wgrad_bn_segs", xs[0], dy_ptr, lddy, bn.raw.ptr, bn.raw.ld, dr, *inner, *geom)
+            elif spec.ld is not None:
                 n, cphys, cin = spec.ld
-                self.call("dy_conv_wgrad_ld_bn", *head, spec.cout, cin, n, cphys, accumulate_w)
+                self.call("dy_conv_wgrad_ld_bn", x.ptr, x.ld, dy_ptr, lddy, bn.raw.ptr, bn.raw.ld, dr, *inner, x.N, x.H, x.W, spec.cout, cin, n, cphys,
+                          accumulate_w)
             else:
-                self.call("dy_conv_wgrad_bn", *head, spec.cin, spec.cout, spec.ks, spec.stride, accumulate_w)
-            dy_ptr, lddy = draw.data_ptr(), spec.cout
+                self.call("dy_conv_wgrad_bn", x.ptr, x.ld, dy_ptr, lddy, bn.raw.ptr, bn.raw.ld, dr, *inner, x.N, x.H, x.W, spec.cin, spec.cout, spec.ks,
+                          spec.stride, accumulate_w)
+            dy_ptr, lddy = bn.draw.data_ptr(), spec.cout
         elif bias_acc is not None:
             assert deferred
             self.call("dy_conv_wgrad_bias", x.ptr, x.ld, dy_ptr, lddy, self._acc_ready(bias_acc), slabs.data_ptr(), dw, x.N, x.H, x.W,
@@ -1281,8 +1301,8 @@ class Engine:
         else:
             self.call("dy_conv_wgrad", x.ptr, x.ld, dy_ptr, lddy, slabs.data_ptr(), dw, x.N, x.H, x.W,
                       spec.cin, spec.cout, spec.ks, spec.stride, accumulate_w, side=side)
-        if isinstance(x, SegAct):
-            assert bn is not None, f"{spec.name}: a segmented input needs the BatchNorm-in-the-weight-gradient path"
+        if seg:
+            assert form == BWD_WGRAD_BN, f"{spec.name}: a segmented input needs the BatchNorm-in-the-weight-gradient path"
         self._input_grad(spec, x, dy_ptr, lddy, Ho, Wo)
 
     wgrad_log = None  # a list while a StepPlan traces its backward: the ConvSpec behind every reduce descriptor and every weight-gradient
@@ -1290,33 +1310,32 @@ class Engine:
 
     def _input_grad(self, spec, x, dy_ptr, lddy, Ho, Wo):
         """dX = W^T d(raw) of one convolution, d(raw) fp16 at (dy_ptr, lddy): into x's gradient, stored or added (first writer stores)."""
-        if isinstance(x, SegAct):
-            if x.needs_grad:  # every 8-channel piece of W^T d(raw) goes to its member's gradient tensor, stored or added per member
-                accs = [q.grad_target() if q.needs_grad else 0 for q in x.parts]  # (a member that needs none gets a sink: _segs)
-                self.call("dy_conv1x1_input_grad_segs", dy_ptr, lddy, spec.wpack_t.data_ptr(), C.byref(self._segs(x, grad=True, acc=accs)),
-                          x.N, Ho, Wo, spec.cout_phys, spec.cin)
+        if not x.needs_grad:
             return
-        if x.needs_grad:
-            acc = x.grad_target()
-            prod = self._sole_consumer_of_conv(x) if (BN_DGRED and not acc and spec.stride == 1 and spec.ld is None) else None
-            if prod is not None:
-                ps, praw = prod
-                if not (ps.act == DY_ACT_SILU and ps.acc_b is not None and ps.cout == x.C == spec.cin and x.C <= BN_DGRED_MAXC and x.npix <= BN_DGRED_MAXPIX
-                        and (praw.N, praw.H, praw.W) == (x.N, x.H, x.W)
-                        and self.L.dy_conv_red_supported(spec.cout_phys, spec.cin, spec.ks)):
-                    prod = None
-            if prod is not None:
-                # this dgrad is the only writer of the gradient of ps's output: ps's BatchNorm backward reduce rides on its epilogue
-                self.call("dy_conv_input_grad_red", dy_ptr, lddy, spec.wpack_t.data_ptr(), x.gptr, x.ld, x.N, Ho, Wo, spec.cout_phys, spec.cin,
-                          spec.ks, praw.ptr, praw.ld, ps.coef.data_ptr(), self._acc_ready(ps.acc_b), ps.cout)
-                self._reduced.add(id(ps))
-            else:
-                # (over cin_phys output rows where x has a ragged last granule: the transposed pack's rows behind cin are zeros, so the
-                # pad lanes of the gradient twin are WRITTEN, as zeros, by the whole-granule epilogue; a plain tensor of logical width
-                # cin < cin_phys -- the 3-channel image import -- keeps the masked stores)
-                cin = spec.cin_phys if x.C != x.Cp else spec.cin
-                self.call("dy_conv_forward", dy_ptr, lddy, spec.wpack_t.data_ptr(), 0, x.gptr, x.ld, 0, x.N, Ho, Wo,
-                          spec.cout_phys, cin, spec.ks, 1, spec.stride, x.H, x.W, DY_EPI_ACCUM if acc else 0, None)
+        (gptr, gld, acc), dxs = self._grad_dst(x)
+        if dxs is not None:
+            self.call("dy_conv1x1_input_grad_segs", dy_ptr, lddy, spec.wpack_t.data_ptr(), dxs, x.N, Ho, Wo, spec.cout_phys, spec.cin)
+            return
+        prod = self._sole_consumer_of_conv(x) if (BN_DGRED and not acc and spec.stride == 1 and spec.ld is None) else None
+        if prod is not None:
+            ps, praw = prod
+            if not (ps.act == DY_ACT_SILU and ps.acc_b is not None and ps.cout == x.C == spec.cin and x.C <= BN_DGRED_MAXC and x.npix <= BN_DGRED_MAXPIX
+                    and (praw.N, praw.H, praw.W) == (x.N, x.H, x.W)
+                    and self.L.dy_conv_red_supported(spec.cout_phys, spec.cin, spec.ks)):
+                prod = None
+        if prod is not None:
+            # this dgrad is the only writer of the gradient of ps's output: ps's BatchNorm backward reduce rides on its epilogue
+            self.call("dy_conv_input_grad_red", dy_ptr, lddy, spec.wpack_t.data_ptr(), gptr, gld, x.N, Ho, Wo, spec.cout_phys, spec.cin,
+                      spec.ks, praw.ptr, praw.ld, ps.coef.data_ptr(), self._acc_ready(ps.acc_b), ps.cout)
+            self._reduced.add(id(ps))
+        else:
+            # (over cin_phys output rows where x has a ragged last granule: the transposed pack's rows behind cin are zeros, so the
+            # pad lanes of the gradient twin are WRITTEN, as zeros, by the whole-granule epilogue; a plain tensor of logical width
+            # cin < cin_phys -- the 3-channel image import -- keeps the masked stores)
+            cin = spec.cin_phys if x.C != x.Cp else spec.cin
+            self.call("dy_conv_forward", dy_ptr, lddy, spec.wpack_t.data_ptr(), 0, gptr, gld, 0, x.N, Ho, Wo,
+                      spec.cout_phys, cin, spec.ks, 1, spec.stride, x.H, x.W, DY_EPI_ACCUM if acc else 0, None)
+
 
     deferred_wgrad = None
     tape_mark = None  # index into the tape where the neck + head begin (set by BaseModel.forward_act while tracing)
@@ -1324,9 +1343,8 @@ class Engine:
     def flush_wgrad(self):
         """Reduce the slabs of every deferred layer into its fp32 weight gradient: one launch, one descriptor per layer."""
         items, self.deferred_wgrad = self.deferred_wgrad, None
-        if self.side_wgrad or self._side_used:
+        if self.side_wgrad:
             self.join()
-            self._side_used = False
         if not items:
             return
         if self.wgrad_log is not None:
@@ -1352,7 +1370,7 @@ class Engine:
         """Conv.forward_fuse (reference nn/modules/conv.py:57-59): BN folded into weights + bias, SiLU in the epilogue."""
         if isinstance(x, ImageAct):
             if STEM_DIRECT and self._stem_eval_ok(spec, res) and spec.bias is not None:  # the fused stem from the image batch itself
-                Ho, Wo = (x.H - 1) // 2 + 1, (x.W - 1) // 2 + 1
+                Ho, Wo = self._stem_hw(x)
                 y = out if out is not None else self.new_act(x.N, Ho, Wo, spec.cout)
                 self.call("dy_stem_forward_eval", x.img.data_ptr(), spec.weight.data_ptr(), spec.bias.data_ptr(), y.ptr, y.ld, x.N, x.H, x.W,
                           x.mul, 1 if spec.act == DY_ACT_SILU else 0)
@@ -1415,20 +1433,17 @@ class Engine:
         """Detect's final class conv inside a StepPlan trace (caller checked ``cls_capable``): dy_cls_head_forward now, one
         dy_cls_head_backward launch for the weight, bias and input gradients later."""
         self._use(x)
-        src = self.unapplied(x)
-        xp, xld, xcoef = (x.ptr, x.ld, 0) if src is None else (src[0].ptr, src[0].ld, src[1].coef.data_ptr())
+        xp, xld, xcoef = self._src(x)
         self.call("dy_cls_head_forward", xp, xld, xcoef, spec.weight.data_ptr(), spec.bias.data_ptr(), y_ptr, x.npix, spec.cin, spec.cout)
 
         def bwd():
             dyp, ld = dy_ptr_fn()
             assert ld == 8 and self.deferred_wgrad is not None and not self.side_wgrad
             ns = self.L.dy_cls_head_slabs()
-            slabs = self.transient((ns * 16 * spec.cin,), torch.float32)
-            self.hold(slabs)
-            self.deferred_wgrad.append((spec, slabs, ns, spec.acc_bias))
-            acc = x.grad_target() if x.needs_grad else 0
-            self.call("dy_cls_head_backward", xp, xld, xcoef, dyp, spec.weight.data_ptr(), x.gptr if x.needs_grad else 0, x.ld, acc,
-                      slabs.data_ptr(), self._acc_ready(spec.acc_bias), x.npix, spec.cin, spec.cout)
+            slabs = self._deferred_slabs(spec, ns * 16 * spec.cin, ns, spec.acc_bias)
+            dx, _ = self._grad_dst(x)
+            self.call("dy_cls_head_backward", xp, xld, xcoef, dyp, spec.weight.data_ptr(), *dx, slabs.data_ptr(), self._acc_ready(spec.acc_bias),
+                      x.npix, spec.cin, spec.cout)
         self.tape.append(bwd)
 
     @staticmethod
@@ -1461,15 +1476,12 @@ class Engine:
             dyp, ld = fn()
             Ho, Wo = self.out_hw(spec, x)
             ns = self.L.dy_conv1x1_rows_slabs(x.N, Ho, Wo)
-            slabs = self.transient((ns * spec.cout * spec.cin,), torch.float32)
-            self.hold(slabs)
-            self.deferred_wgrad.append((spec, slabs, ns, spec.acc_bias))
-            acc = x.grad_target() if x.needs_grad else 0
-            if x.needs_grad and not acc and self._sole_consumer_of_conv(x) is not None:
+            slabs = self._deferred_slabs(spec, ns * spec.cout * spec.cin, ns, spec.acc_bias)
+            dx, _ = self._grad_dst(x)
+            if x.needs_grad and not dx[2] and self._sole_consumer_of_conv(x) is not None:
                 self._rows_grad[(id(x.st), x.c0, x.C)] = (asg, A, a0[l])
-            xp, xld, xc = self._src(x)
-            for k, v in zip(cols, (xp, xld, xc, dyp, ld, a0[l], spec.weight.data_ptr(), x.gptr if x.needs_grad else 0, x.ld, acc,
-                                   slabs.data_ptr(), self._acc_ready(spec.acc_bias), Ho, Wo)):
+            for k, v in zip(cols, (*self._src(x), dyp, ld, a0[l], spec.weight.data_ptr(), *dx, slabs.data_ptr(), self._acc_ready(spec.acc_bias),
+                                   Ho, Wo)):
                 cols[k].append(v)
         P, I = C.c_void_p, C.c_int
         spec0, x0 = items[0][0], items[0][1]
@@ -1482,31 +1494,28 @@ class Engine:
         """``conv_bias_cls`` for several levels at once (items = [(spec, x, y_ptr, dy_ptr_fn)], same cin / nc): one forward launch now,
         one backward launch first thing in the backward pass."""
         P, I, Lg = C.c_void_p, C.c_int, C.c_long
-        srcs = [self._src(x) for _, x, _, _ in items]
+        srcs = list(zip(*[self._src(x) for _, x, _, _ in items]))
+        srcs = (self._arr(P, srcs[0]), self._arr(I, srcs[1]), self._arr(P, srcs[2]))  # (pointer, ld, coefficient table) per level
         for _, x, _, _ in items:
             self._use(x)
         spec0 = items[0][0]
-        self.call("dy_cls_head_forward_levels", len(items), self._arr(P, [s_[0] for s_ in srcs]), self._arr(I, [s_[1] for s_ in srcs]),
-                  self._arr(P, [s_[2] for s_ in srcs]), self._arr(P, [sp.weight.data_ptr() for sp, _, _, _ in items]),
+        self.call("dy_cls_head_forward_levels", len(items), *srcs, self._arr(P, [sp.weight.data_ptr() for sp, _, _, _ in items]),
                   self._arr(P, [sp.bias.data_ptr() for sp, _, _, _ in items]), self._arr(P, [yp for _, _, yp, _ in items]),
                   self._arr(Lg, [x.npix for _, x, _, _ in items]), spec0.cin, spec0.cout)
 
         def bwd():
             assert self.deferred_wgrad is not None and not self.side_wgrad
-            dys, dxs, accs, slabs_l, baccs = [], [], [], [], []
+            dys, dxs, slabs_l, baccs = [], [], [], []
             ns = self.L.dy_cls_head_slabs()
             for spec, x, _, fn in items:
                 dyp, ld = fn()
                 assert ld == 8
-                slabs = self.transient((ns * 16 * spec.cin,), torch.float32)
-                self.hold(slabs)
-                self.deferred_wgrad.append((spec, slabs, ns, spec.acc_bias))
-                accs.append(x.grad_target() if x.needs_grad else 0)
-                dys.append(dyp); dxs.append(x.gptr if x.needs_grad else 0); slabs_l.append(slabs.data_ptr())
+                slabs = self._deferred_slabs(spec, ns * 16 * spec.cin, ns, spec.acc_bias)
+                dxs.append(self._grad_dst(x)[0])
+                dys.append(dyp); slabs_l.append(slabs.data_ptr())
                 baccs.append(self._acc_ready(spec.acc_bias))
-            self.call("dy_cls_head_backward_levels", len(items), self._arr(P, [s_[0] for s_ in srcs]), self._arr(I, [s_[1] for s_ in srcs]),
-                      self._arr(P, [s_[2] for s_ in srcs]), self._arr(P, dys), self._arr(P, [sp.weight.data_ptr() for sp, _, _, _ in items]),
-                      self._arr(P, dxs), self._arr(I, [x.ld for _, x, _, _ in items]), self._arr(I, accs), self._arr(P, slabs_l),
+            self.call("dy_cls_head_backward_levels", len(items), *srcs, self._arr(P, dys), self._arr(P, [sp.weight.data_ptr() for sp, _, _, _ in items]),
+                      self._arr(P, [d[0] for d in dxs]), self._arr(I, [d[1] for d in dxs]), self._arr(I, [d[2] for d in dxs]), self._arr(P, slabs_l),
                       self._arr(P, baccs), self._arr(Lg, [x.npix for _, x, _, _ in items]), spec0.cin, spec0.cout)
         self.tape.append(bwd)
 
@@ -1535,18 +1544,13 @@ class Engine:
                 and not self.side_wgrad):
             asg, A, a0 = self.loss_rows
             ns = self.L.dy_conv1x1_rows_slabs(x.N, Ho, Wo)
-            slabs = self.transient((ns * spec.cout * spec.cin,), torch.float32)
-            self.hold(slabs)
-            self.deferred_wgrad.append((spec, slabs, ns, spec.acc_bias))
-            acc = x.grad_target() if x.needs_grad else 0
-            if x.needs_grad and not acc and self._sole_consumer_of_conv(x) is not None:
+            slabs = self._deferred_slabs(spec, ns * spec.cout * spec.cin, ns, spec.acc_bias)
+            dx, _ = self._grad_dst(x)
+            if x.needs_grad and not dx[2] and self._sole_consumer_of_conv(x) is not None:
                 # x is a Conv's output whose only forward use was this conv: its gradient has the same rows, and nothing else
                 self._rows_grad[(id(x.st), x.c0, x.C)] = (asg, A, a0[rows_level])
-            src = self.unapplied(x)
-            xp, xld, xcoef = (x.ptr, x.ld, 0) if src is None else (src[0].ptr, src[0].ld, src[1].coef.data_ptr())
-            self.call("dy_conv1x1_rows_backward", xp, xld, xcoef, dyp, ld, asg, A, a0[rows_level], spec.weight.data_ptr(),
-                      x.gptr if x.needs_grad else 0, x.ld, acc, slabs.data_ptr(), self._acc_ready(spec.acc_bias), x.N, Ho, Wo,
-                      spec.cin, spec.cout)
+            self.call("dy_conv1x1_rows_backward", *self._src(x), dyp, ld, asg, A, a0[rows_level], spec.weight.data_ptr(), *dx, slabs.data_ptr(),
+                      self._acc_ready(spec.acc_bias), x.N, Ho, Wo, spec.cin, spec.cout)
             return
         assert self.unapplied(x) is None, f"{spec.name}: the dense backward needs the activated input that was never written"
         if (BIAS_WGRAD and defer and not accumulate and self.deferred_wgrad is not None and spec.acc_bias is not None and spec.ld is None
@@ -1625,8 +1629,7 @@ class Engine:
     def maxpool5(self, x: Act, out: Act):
         self.whole8("SPPF", x)
         x = self.dense(x)
-        arg = self.transient((x.npix * x.C,), torch.uint8)
-        self.hold(arg)
+        arg = self.held((x.npix * x.C,), torch.uint8)
         self._use(x)
         self.call("dy_maxpool5", x.ptr, x.ld, out.ptr, out.ld, arg.data_ptr(), x.N, x.H, x.W, x.C)
 
@@ -1811,12 +1814,10 @@ class Engine:
             raws.append(r)
         if self.training:
             self.call("dy_bn_finalize", part.data_ptr() + offs[0], nps[0], 1.0, part.data_ptr() + offs[1], nps[1], 4.0,
-                      part.data_ptr() + offs[2], nps[2], 16.0, bn3d["weight"].data_ptr(), bn3d["bias"].data_ptr(),
-                      bn3d["running_mean"].data_ptr(), bn3d["running_var"].data_ptr(), coef.data_ptr(), Cc,
+                      part.data_ptr() + offs[2], nps[2], 16.0, *self._bn_ptrs(bn3d), coef.data_ptr(), Cc,
                       float(3 * N * H * W), BN3D_EPS, BN3D_MOM, 1)
         else:
-            self.call("dy_bn_eval_coef", bn3d["weight"].data_ptr(), bn3d["bias"].data_ptr(), bn3d["running_mean"].data_ptr(),
-                      bn3d["running_var"].data_ptr(), coef.data_ptr(), Cc, BN3D_EPS)
+            self.call("dy_bn_eval_coef", *self._bn_ptrs(bn3d), coef.data_ptr(), Cc, BN3D_EPS)
         y = out if out is not None else self.new_act(N, H, W, Cc)
         live = self._live(conv3d, *ps, res)
         if res is not None:
@@ -1867,8 +1868,7 @@ class Engine:
         self.whole8("LDConv", x)
         x = self.dense(x)
         h, w = self.out_hw(sp_p, x)
-        off = self.transient((x.N, h, w, 2 * Np), torch.float32)
-        self.hold(off)
+        off = self.held((x.N, h, w, 2 * Np), torch.float32)
         doff = None
         if self.tape is not None:
             doff = torch.zeros((x.N, h, w, 8 * ((2 * Np + 7) // 8)), dtype=torch.float16, device=self.device)
@@ -1915,13 +1915,11 @@ class Engine:
             raise NotImplementedError(f"DySample on {x.C} channels, {G} groups, scale {s}: the sampler takes scale 2 or 4 and channels "
                                       "that are a multiple of 8 * groups")
         nch = 2 * G * s * s
-        off = self.transient((x.N, x.H, x.W, nch), torch.float32)
-        self.hold(off)
+        off = self.held((x.N, x.H, x.W, nch), torch.float32)
         live = self._live(sp_off, x)
         doff = None
         if self.tape is not None and live:
-            doff = self.transient((x.N, x.H, x.W, nch), torch.float16)  # written whole by the backward launch before it is read
-            self.hold(doff)
+            doff = self.held((x.N, x.H, x.W, nch), torch.float16)  # written whole by the backward launch before it is read
         if sp_off.trainable or self.tape is None:
             self.conv_bias(sp_off, x, off.data_ptr(), nch, True, lambda: (doff.data_ptr(), nch))
         else:
