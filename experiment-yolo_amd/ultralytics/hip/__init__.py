@@ -154,6 +154,12 @@ SIGNATURES = {
     "dy_carafe_supported": (i32, [i32, i32, i32]),
     "dy_carafe": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "dy_carafe_backward": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "dy_dwconv_supported": (i32, [i32, i32, i32, i32]),
+    "dy_dwconv_num_partials": (i32, [i32, i32, i32, i32, i32, i32, i32]),
+    "dy_dwconv_wgrad_slabs": (i32, [i32, i32, i32, i32, i32, i32, i32]),
+    "dy_dwconv_forward": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "dy_dwconv_input_grad": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "dy_dwconv_wgrad": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "dy_maxpool5": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),
     "dy_maxpool5_backward": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dy_bn_group_max": (i32, []),

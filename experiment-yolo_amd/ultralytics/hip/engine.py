@@ -166,6 +166,7 @@ class ConvBwdFacts(NamedTuple):
     res_grad: bool = False   # a shortcut that needs a gradient ...
     res_same: bool = False   # ... as wide as the output ...
     res_acc: bool = False    # ... which something wrote already
+    depthwise: bool = False  # a depthwise layer (csrc/dwconv.hip): its weight / input gradients take a materialised d(raw)
 
 
 def conv_bwd_form(f: ConvBwdFacts) -> ConvBwdForm:
@@ -191,6 +192,8 @@ def conv_bwd_form(f: ConvBwdFacts) -> ConvBwdForm:
     in_wgrad = bool(acc and BN_WGRAD and silu and not f.side_wgrad and f.raw_dense and (f.trainable or f.planes))
     if not f.trainable and not f.planes and not f.x_grad:
         launch = BWD_NONE  # (only the shortcut carried a gradient on)
+    elif f.depthwise:
+        launch = BWD_APPLY  # dy_dwconv_wgrad / dy_dwconv_input_grad read d(raw) from memory: no kernel of theirs forms it
     elif not f.trainable and FROZEN_DGRAD and acc and silu and one and f.dgrad_ok:
         launch = BWD_DGRAD_ONLY  # no shared scratch: branch and side-stream backward passes may take it too
     elif in_wgrad and WGRAD_DGRAD and one and not f.branch and f.fused_ok:
@@ -464,10 +467,14 @@ class ConvSpec:
     """Device-side view of one convolution (+ optional BatchNorm) of the model: master fp32 parameters (views into
     the flat parameter buffer), their gradient views, MFMA-packed fp16 weights and BN coefficient buffers."""
 
-    def __init__(self, name, weight, bias, bn, ks, stride, act, bn_eps=BN2D_EPS, bn_mom=BN2D_MOM):
+    def __init__(self, name, weight, bias, bn, ks, stride, act, bn_eps=BN2D_EPS, bn_mom=BN2D_MOM, groups=1):
         self.name, self.weight, self.bias, self.bn = name, weight, bias, bn  # bn: dict(weight,bias,running_mean,running_var,nbt)|None
         self.ks, self.stride, self.act = ks, stride, act
-        self.cout, self.cin = weight.shape[0], weight.shape[1]
+        # ``cin`` is the width of the INPUT: a grouped weight is (cout, cin / groups, k, k).  groups > 1 is depthwise (groups == cin) with
+        # channel multiplier ``mult`` = cout / cin; such a spec has no MFMA packs and runs through the dy_dwconv_* entries
+        self.groups, self.dw = groups, groups > 1
+        self.cout, self.cin = weight.shape[0], weight.shape[1] * groups
+        self.mult = self.cout // self.cin if self.dw else 1
         self.ld = None  # (N, C_phys, real_cin) for LDConv's (N,1) column conv seen as a 1x1 conv over N*C_phys channels
         self.bn_eps, self.bn_mom = bn_eps, bn_mom
         self.wpack = self.wpack_t = self.coef = self.bwdcoef = None
@@ -774,7 +781,15 @@ class Engine:
     # ---- parameter plumbing ---------------------------------------------------------------------------------------
     def prepare_conv(self, spec: ConvSpec):
         """Allocate packed-weight / coefficient buffers of a ConvSpec (idempotent)."""
-        if spec.wpack is not None:
+        if spec.wpack is not None or getattr(spec, "prepared", False):
+            return
+        if spec.dw:  # no packs: the kernels read the fp32 masters; BatchNorm in the generic three-launch form (no accumulators)
+            if spec.weight.shape[1] != 1 or spec.ld is not None or not self.L.dy_dwconv_supported(spec.cin, spec.mult, spec.ks, spec.stride):
+                raise NotImplementedError(f"{spec.name}: a grouped convolution {tuple(spec.weight.shape)} with groups={spec.groups}, k={spec.ks}, "
+                                          f"s={spec.stride} (supported: depthwise, groups == c1, c1 % 8 == 0, c2 / c1 in 1|2, k in 3|5, s in 1|2)")
+            spec.cin_phys, spec.cout_phys, spec.prepared = spec.cin, spec.cout, True
+            if spec.bn is not None:
+                spec.coef, spec.bwdcoef = self.f32(4 * spec.cout), self.f32(2 * spec.cout)
             return
         g = [C.c_int() for _ in range(8)]
         if spec.ld is not None:
@@ -799,6 +814,8 @@ class Engine:
 
     def pack(self, spec: ConvSpec, fold_scale=None, transposed=True):
         self.prepare_conv(spec)
+        if spec.dw:
+            return
         if spec.ld is not None:
             n, cphys, cin = spec.ld
             self.call("dy_pack_weights_ld", spec.weight.data_ptr(), spec.wpack.data_ptr(), spec.cout, cin, n, cphys, 0)
@@ -902,7 +919,7 @@ class Engine:
                             x_grad=bool(x.needs_grad), planes=planes, branch=bool(self.cur_sid), side_wgrad=bool(self.side_wgrad),
                             deferred=self.deferred_wgrad is not None,
                             fused_ok=geom is not None and bool(self.L.dy_conv1x1_wgrad_dgrad_supported(*geom)),
-                            dgrad_ok=geom is not None and bool(self.L.dy_conv1x1_dgrad_bn_supported(*geom)), **dataflow)
+                            dgrad_ok=geom is not None and bool(self.L.dy_conv1x1_dgrad_bn_supported(*geom)), depthwise=spec.dw, **dataflow)
 
     def snapshot(self, x):
         """``x`` as one tensor for INSPECTION (a per-layer capture): a copy that never joins the backward pass -- a copy made by
@@ -980,6 +997,8 @@ class Engine:
         accumulator path, no residual; the caller guarantees that every consumer of the result asks ``unapplied()`` for (raw, spec)
         instead of reading it): the apply launch only leaves the coefficient table and the running statistics behind (zero pixels),
         the returned activation is never written."""
+        if spec.dw:
+            return self._dwconv_bn_act(spec, x, out, res)
         if isinstance(x, ImageAct):
             if (self.training and STEM_DIRECT and spec.acc_f is not None and (spec.cin, spec.cout, spec.ks, spec.stride) == (3, 16, 3, 2)
                     and spec.act == DY_ACT_SILU and res is None and spec.ld is None):
@@ -1056,6 +1075,66 @@ class Engine:
                       0 if res is None else res.ld, y.ptr, y.ld, spec.coef.data_ptr(), npix, spec.cout, spec.act)
         self._record(live, y, lambda: self._conv_bn_act_bwd(spec, x, raw, y, res))
         return y
+
+    def _dw_input(self, spec, x, out, res):
+        """What a depthwise layer reads: one tensor of whole granules (a concatenation, an up-sampling or the image batch is
+        materialised first); no residual operand, no two-plane output."""
+        if res is not None:
+            raise NotImplementedError(f"{spec.name}: a depthwise convolution takes no residual operand")
+        if isinstance(out, SegAct):
+            raise NotImplementedError(f"{spec.name}: a depthwise convolution writes no two-plane output")
+        x = x.materialize() if isinstance(x, ImageAct) else self.dense(x)
+        if x.C != spec.cin or x.C % 8 or not self.L.dy_dwconv_supported(x.C, spec.mult, spec.ks, spec.stride):
+            raise NotImplementedError(f"{spec.name}: a depthwise convolution (c1={spec.cin}, m={spec.mult}, k={spec.ks}, s={spec.stride}) over an input "
+                                      f"of {x.C} channels (supported: c1 % 8 == 0, m in 1|2, k in 3|5, s in 1|2)")
+        return x
+
+    def _dw_geom(self, spec, x):
+        return (x.N, x.H, x.W, spec.cin, spec.mult, spec.ks, spec.stride)
+
+    def _dwconv_bn_act(self, spec, x, out=None, res=None):
+        """``conv_bn_act`` of a depthwise spec (csrc/dwconv.hip): dy_dwconv_forward, then BatchNorm in the generic three-launch form --
+        training: statistics partials -> dy_bn_finalize -> dy_bn_act_apply; eval: dy_bn_eval_coef -> dy_bn_act_apply."""
+        x = self._dw_input(spec, x, out, res)
+        Ho, Wo = self.out_hw(spec, x)
+        raw = self.new_act(x.N, Ho, Wo, spec.cout)
+        y = out if out is not None else self.new_act(x.N, Ho, Wo, spec.cout)
+        assert (y.N, y.H, y.W, y.C) == (x.N, Ho, Wo, spec.cout), (spec.name, (y.N, y.H, y.W, y.C), (x.N, Ho, Wo, spec.cout))
+        live = self._live(spec, x)
+        if live:
+            self._use(x)
+        npix, bn, geom = x.N * Ho * Wo, spec.bn, self._dw_geom(spec, x)
+        if self.training:
+            nparts = self.L.dy_dwconv_num_partials(*geom)
+            part = self._staging("partials", nparts * 2 * spec.cout * 4 + 4096)
+            self.call("dy_dwconv_forward", x.ptr, x.ld, spec.weight.data_ptr(), 0, raw.ptr, raw.ld, part.data_ptr(), *geom, DY_EPI_STATS)
+            self.call("dy_bn_finalize", part.data_ptr(), nparts, 1.0, 0, 0, 0.0, 0, 0, 0.0, *self._bn_ptrs(bn), spec.coef.data_ptr(), spec.cout,
+                      float(npix), spec.bn_eps, spec.bn_mom, 1)
+        else:
+            self.call("dy_dwconv_forward", x.ptr, x.ld, spec.weight.data_ptr(), 0, raw.ptr, raw.ld, 0, *geom, 0)
+            self.call("dy_bn_eval_coef", *self._bn_ptrs(bn), spec.coef.data_ptr(), spec.cout, spec.bn_eps)
+        self.call("dy_bn_act_apply", raw.ptr, raw.ld, 0, 0, y.ptr, y.ld, spec.coef.data_ptr(), npix, spec.cout, spec.act)
+        self._record(live, y, lambda: self._conv_bn_act_bwd(spec, x, raw, y, None))
+        return y
+
+    def _dwconv_fused(self, spec, x, out=None, res=None):
+        """``conv_fused`` of a depthwise spec: bias + activation in the convolution's one launch."""
+        x = self._dw_input(spec, x, out, res)
+        Ho, Wo = self.out_hw(spec, x)
+        y = out if out is not None else self.new_act(x.N, Ho, Wo, spec.cout)
+        self.call("dy_dwconv_forward", x.ptr, x.ld, spec.weight.data_ptr(), spec.bias.data_ptr(), y.ptr, y.ld, 0, *self._dw_geom(spec, x),
+                  DY_EPI_BIAS | (DY_EPI_SILU if spec.act == DY_ACT_SILU else 0))
+        return y
+
+    def _dwconv_wgrad(self, spec, x, dy_ptr, lddy):
+        """The weight gradient of a depthwise spec from d(raw): per-workgroup slabs and their ordered reduction, both inside the one entry
+        (the descriptor of dy_wgrad_reduce_batched describes MFMA-tiled slabs, which these are not: nothing is deferred)."""
+        geom = self._dw_geom(spec, x)
+        ns = self.L.dy_dwconv_wgrad_slabs(*geom)
+        slabs = self._staging("dw_slabs", ns * spec.cout * spec.ks * spec.ks * 4)
+        if self.wgrad_log is not None:
+            self.wgrad_log.append(spec)
+        self.call("dy_dwconv_wgrad", x.ptr, x.ld, dy_ptr, lddy, slabs.data_ptr(), spec.gweight.data_ptr(), 0, *geom)
 
     @staticmethod
     def _stem_eval_ok(spec, res):
@@ -1245,6 +1324,11 @@ class Engine:
         of the backward pass; weights shared by several calls (ScalSeq's conv3d: ``defer=False``) reduce immediately."""
         if form is None:
             form = BWD_APPLY if bn is None else BWD_WGRAD_BN
+        if spec.dw:
+            assert form == BWD_APPLY and not accumulate_w and bias_acc is None and planes is None, f"{spec.name}: a depthwise layer's backward takes d(raw)"
+            self._dwconv_wgrad(spec, x, dy_ptr, lddy)
+            self._input_grad(spec, x, dy_ptr, lddy, Ho, Wo)
+            return
         ns, se = C.c_int(), C.c_long()
         self.L.dy_wgrad_workspace(x.N, x.H, x.W, spec.cin, spec.cout, spec.ks, spec.stride, C.byref(ns), C.byref(se))
         deferred = defer and not accumulate_w and self.deferred_wgrad is not None
@@ -1313,6 +1397,9 @@ class Engine:
         if not x.needs_grad:
             return
         (gptr, gld, acc), dxs = self._grad_dst(x)
+        if spec.dw:
+            self.call("dy_dwconv_input_grad", dy_ptr, lddy, spec.weight.data_ptr(), gptr, gld, acc, *self._dw_geom(spec, x))
+            return
         if dxs is not None:
             self.call("dy_conv1x1_input_grad_segs", dy_ptr, lddy, spec.wpack_t.data_ptr(), dxs, x.N, Ho, Wo, spec.cout_phys, spec.cin)
             return
@@ -1368,6 +1455,8 @@ class Engine:
 
     def conv_fused(self, spec: ConvSpec, x: Act, out: Act | None = None, res: Act | None = None):
         """Conv.forward_fuse (reference nn/modules/conv.py:57-59): BN folded into weights + bias, SiLU in the epilogue."""
+        if spec.dw:
+            return self._dwconv_fused(spec, x, out, res)
         if isinstance(x, ImageAct):
             if STEM_DIRECT and self._stem_eval_ok(spec, res) and spec.bias is not None:  # the fused stem from the image batch itself
                 Ho, Wo = self._stem_hw(x)

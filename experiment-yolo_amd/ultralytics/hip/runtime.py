@@ -180,7 +180,7 @@ class Runtime:
         w = conv.weight.data
         w2 = w if ld is not None else (w.reshape(w.shape[0], w.shape[1], ks, ks) if w.dim() != 4 or w.shape[2] != ks else w)
         sp = ConvSpec(name, w2, None if conv.bias is None else conv.bias.data, None if bn is None else self._bn_dict(bn), ks,
-                      stride, act, eps, mom)
+                      stride, act, eps, mom, groups=int(getattr(conv, "groups", 1)))
         sp.ld = ld
         sp.params = dict(weight=conv.weight, bias=conv.bias, bn_w=None if bn is None else bn.weight, bn_b=None if bn is None else bn.bias)
         self._bind_grads(sp)
@@ -200,17 +200,18 @@ class Runtime:
     def pack_all(self, transposed=True):
         """Refresh every MFMA weight pack from the fp32 masters in ONE launch (recorded at the start of each step)."""
         import ctypes as C
-        if not self.specs:
+        specs = [sp for sp in self.specs.values() if not sp.dw]  # (a depthwise spec has no packs: its kernels read the masters)
+        if not specs:
             return
-        key = (transposed, tuple(sp.weight.data_ptr() for sp in self.specs.values()))
+        key = (transposed, tuple(sp.weight.data_ptr() for sp in specs))
         cached = getattr(self, "_pack_tbl", None)
         if cached is None or cached[0] != key:
             L = self.eng.L
             sz = L.dy_pack_desc_bytes()
-            n = len(self.specs) * (2 if transposed else 1)
+            n = len(specs) * (2 if transposed else 1)
             host = (C.c_char * (sz * n))()
             blocks, i = 0, 0
-            for sp in self.specs.values():
+            for sp in specs:
                 for tr in ((0, 1) if transposed else (0,)):
                     ld = sp.ld or (0, 0, sp.weight.shape[1])
                     nb = L.dy_pack_desc_fill(C.byref(host, i * sz), sp.weight.data_ptr(), 0, (sp.wpack_t if tr else sp.wpack).data_ptr(),

@@ -244,7 +244,7 @@ class SoapHip:
     Gram -> (refresh) -> rotate m forward; the first call only seeds (Gram from zero, eigh).  One 4-byte read-back per step (found_inf:
     a skipped step must not advance ``t``, which the refresh schedule and the checkpoint need); ``launches`` counts the kernels issued."""
 
-    def __init__(self, views, flat_p, hyper, state, partials, beta1=0.9, beta2=0.95, eps=1e-8, every=10, max_precond_dim=10000):
+    def __init__(self, views, flat_p, hyper, state, partials, beta1=0.9, beta2=0.95, eps=1e-8, every=10, max_precond_dim=10000, grouped=()):
         from . import lib
         self.L = lib()
         self.beta1, self.beta2, self.eps, self.every = beta1, beta2, eps, every
@@ -253,6 +253,10 @@ class SoapHip:
         self.n = n
         self.table = tb = SoapTable(views, max_precond_dim)
         for e in tb.entries:
+            sh = e["shape"]
+            if e["name"] in grouped:  # ``grouped``: names of the weights of grouped (depthwise) convolutions, (C, 1, k, k)
+                raise NotImplementedError(f"SOAP: '{e['name']}' is a depthwise convolution weight {sh} = (C, 1, k, k); the grouped HIP step has not "
+                                          f"been verified on such a tensor: train this graph with SGD / Adam* / RMSProp")
             if e["off"] < 0 or e["off"] + e["numel"] > n:
                 raise ValueError(f"SOAP: '{e['name']}' lies outside the flat parameter buffer")
         f = lambda k, dt=torch.float32: torch.zeros(max(k, 1), dtype=dt, device=dev)  # noqa: E731

@@ -585,7 +585,9 @@ class StepPlan:
             self._soap_views = views
             self._soap_hip = os.environ.get("DY_SOAP_HIP", "1") != "0"  # read when the optimizer object is built
             if self._soap_hip:
-                self._soap = SoapHip(views, rt.flat_p, self.hyper, self.state, self.partials, beta1=self._hyp["momentum"], beta2=0.95)
+                dw = {id(sp.params["weight"]) for sp in rt.specs.values() if sp.dw}
+                grouped = {n for n, p in self.model.named_parameters() if id(p) in dw}
+                self._soap = SoapHip(views, rt.flat_p, self.hyper, self.state, self.partials, beta1=self._hyp["momentum"], beta2=0.95, grouped=grouped)
             else:
                 self._soap = Soap([(rt.flat_p[o:o + k].view(sh), g) for _, o, k, sh, g in views], beta1=self._hyp["momentum"], beta2=0.95)
             self._soap_apply_pending()

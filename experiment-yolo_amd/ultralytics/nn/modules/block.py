@@ -26,6 +26,9 @@ class Bottleneck(HipModule):
 
     def __init__(self, c1, c2, shortcut=True, g=1, k=(3, 3), e=0.5):
         super().__init__()
+        if g != 1:  # (cv2 would be a grouped convolution that takes the shortcut as a residual operand: the depthwise kernels take none)
+            raise NotImplementedError(f"Bottleneck(c1={c1}, c2={c2}, g={g}) is outside the HIP hot path (g=1: its second convolution adds the "
+                                      f"shortcut in its epilogue, which a grouped convolution does not take)")
         c_ = int(c2 * e)
         k0 = k[0][0] if isinstance(k[0], (tuple, list)) else k[0]
         k1 = k[1][0] if isinstance(k[1], (tuple, list)) else k[1]

@@ -1,4 +1,4 @@
-"""Convolution modules of the DEAL-YOLO graph: Conv, LDConv, Concat (drop-in for reference nn/modules/conv.py).
+"""Convolution modules of the DEAL-YOLO graph: Conv, DWConv, DSConv, LDConv, Concat (drop-in for reference nn/modules/conv.py).
 
 Parameters live in ordinary ``nn.Conv2d`` / ``nn.BatchNorm2d`` holders so that ``state_dict`` keys, default
 initialisation and pickled reference checkpoints line up; the arithmetic is issued through
@@ -14,7 +14,7 @@ import torch.nn as nn
 from ...hip import DY_ACT_NONE, DY_ACT_SILU
 from ...hip.runtime import HipModule
 
-__all__ = ("Conv", "LDConv", "Concat", "autopad")
+__all__ = ("Conv", "DWConv", "DSConv", "LDConv", "Concat", "autopad")
 # DY_SPLIT_COUT=0: one launch per fused conv whatever its output width (the last 64-wide cout group zero-padded)
 SPLIT_COUT = __import__("os").environ.get("DY_SPLIT_COUT", "1") != "0"
 
@@ -28,13 +28,27 @@ def autopad(k, p=None, d=1):
     return p
 
 
+DW_SUPPORTED = "supported: depthwise g == c1, c1 % 8 == 0, c2 / c1 in 1|2, k in 3|5, s in 1|2, d=1"
+
+
+def depthwise_check(layer, c1, c2, k, s, g, d=1):
+    """The grouped convolutions the HIP path takes (csrc/dwconv.hip): depthwise with channel multiplier 1 or 2.  Anything else raises,
+    naming the layer, its arguments and the supported set."""
+    ok = (isinstance(k, int) and g == c1 and c1 % 8 == 0 and c2 % c1 == 0 and c2 // c1 in (1, 2) and k in (3, 5) and s in (1, 2) and d == 1)
+    if not ok:
+        raise NotImplementedError(f"{layer}(c1={c1}, c2={c2}, k={k}, s={s}, g={g}, d={d}) is outside the HIP hot path ({DW_SUPPORTED})")
+
+
 class Conv(HipModule):
-    """conv(bias-free) -> BatchNorm2d -> SiLU; args (c1, c2, k, s, p, g, d, act) as reference nn/modules/conv.py:41-59."""
+    """conv(bias-free) -> BatchNorm2d -> SiLU; args (c1, c2, k, s, p, g, d, act) as reference nn/modules/conv.py:41-59.  g == c1 with a
+    supported geometry is a depthwise convolution (``depthwise_check``); any other g != 1 raises."""
     default_act = nn.SiLU()
 
     def __init__(self, c1, c2, k=1, s=1, p=None, g=1, d=1, act=True):
         super().__init__()
-        if g != 1 or d != 1 or k not in (1, 3) or s not in (1, 2) or (k == 1 and s != 1):
+        if g != 1:
+            depthwise_check(type(self).__name__, c1, c2, k, s, g, d)
+        elif d != 1 or k not in (1, 3) or s not in (1, 2) or (k == 1 and s != 1):
             raise NotImplementedError(f"Conv(k={k}, s={s}, g={g}, d={d}) is outside the HIP hot path (k in 1|3, s in 1|2, g=d=1)")
         self.conv = nn.Conv2d(c1, c2, k, s, autopad(k, p, d), groups=g, dilation=d, bias=False)
         self.bn = nn.BatchNorm2d(c2)
@@ -50,8 +64,9 @@ class Conv(HipModule):
                      self.conv.stride[0], name="Conv")
         self.__dict__["_split"] = None
         c2, k = self.conv.out_channels, self.conv.kernel_size[0]
-        if SPLIT_COUT and not hasattr(self, "bn") and self.conv.bias is not None and k == 3 and self.conv.stride[0] == 1 and c2 > 64 and c2 % 64 in (16, 32):
-            # fused (eval) 3x3 conv whose output width is 64 m + 16 / 32 (Detect's class branch for nc = 80: 80 = 64 + 16 channels): the conv
+        if SPLIT_COUT and self.conv.groups == 1 and not hasattr(self, "bn") and self.conv.bias is not None and k == 3 and self.conv.stride[0] == 1 and c2 > 64 and c2 % 64 in (16, 32):
+            # fused (eval) DENSE 3x3 conv (a depthwise layer has no 64-wide cout groups and never splits: groups == 1) whose output width
+            # is 64 m + 16 / 32 (Detect's class branch for nc = 80: 80 = 64 + 16 channels): the conv
             # kernel's cout groups are 64 wide, so the last group would multiply 48 / 32 rows of zero weights -- as much matrix work for
             # 16 outputs as for 64.  The tail runs as a launch of its own on a 16- / 32-row group: two parameter views, two packs.
             from types import SimpleNamespace as NS
@@ -84,6 +99,29 @@ class Conv(HipModule):
         return eng.conv_fused(spec, x, out, res)
 
     forward_fuse = HipModule.forward
+
+
+class DWConv(Conv):
+    """Depth-wise convolution (reference nn/modules/conv.py:106-111): Conv with g = gcd(c1, c2)."""
+
+    def __init__(self, c1, c2, k=1, s=1, d=1, act=True):  # ch_in, ch_out, kernel, stride, dilation, activation
+        super().__init__(c1, c2, k, s, g=math.gcd(c1, c2), d=d, act=act)
+
+
+class DSConv(HipModule):
+    """Depthwise separable convolution (reference nn/modules/conv.py:113-122): DWConv(c1, c1, 3) then Conv(c1, c2, 1); k, s, d and act
+    are accepted and ignored, exactly as the reference does."""
+
+    def __init__(self, c1, c2, k=1, s=1, d=1, act=True):
+        super().__init__()
+        self.dwconv = DWConv(c1, c1, 3)
+        self.pwconv = Conv(c1, c2, 1)
+
+    def out_hw(self, h, w):
+        return h, w
+
+    def forward_act(self, x, out=None):
+        return self.pwconv.forward_act(self.dwconv.forward_act(x), out)
 
 
 class Concat(HipModule):

@@ -21,7 +21,8 @@ import yaml
 from ..hip.engine import Act
 from ..hip.runtime import HipModule, Runtime
 from .extra_modules.block import CARAFE, Add, DySample, ScalSeq, SPDConv, Zoom_cat
-from .modules import SPPF, C2f, Concat, Conv, Detect, LDConv
+from .modules import SPPF, C2f, Concat, Conv, Detect, DSConv, DWConv, LDConv
+from .modules.conv import depthwise_check
 
 CFG_MODELS = Path(__file__).resolve().parent.parent / "cfg" / "models"
 
@@ -43,7 +44,7 @@ class Upsample(HipModule):
         return self.rt.eng.upsample2x(x, out)
 
 
-_MODULES = {"Conv": Conv, "LDConv": LDConv, "C2f": C2f, "SPPF": SPPF, "Concat": Concat, "nn.Upsample": Upsample,
+_MODULES = {"Conv": Conv, "DWConv": DWConv, "DSConv": DSConv, "LDConv": LDConv, "C2f": C2f, "SPPF": SPPF, "Concat": Concat, "nn.Upsample": Upsample,
             "ScalSeq": ScalSeq, "Add": Add, "Zoom_cat": Zoom_cat, "Detect": Detect, "SPDConv": SPDConv, "DySample": DySample, "CARAFE": CARAFE}
 
 
@@ -71,7 +72,7 @@ def yaml_model_load(path):
 
 def parse_model(d, ch, verbose=True):
     """YAML dict -> (nn.Sequential, savelist, per-layer down-sampling) for the hot-path module names
-    (reference tasks.py:780-1062, branches :825-864 -- SPDConv is in that list at :833 --, :905-911, :965-967 for DySample and CARAFE,
+    (reference tasks.py:780-1062, branches :825-864 -- DWConv, DSConv and SPDConv are in that list (:825-843) --, :905-911, :965-967 for DySample and CARAFE,
     :1001-1008)."""
     nc, scales = d.get("nc"), d.get("scales")
     depth, width, max_channels = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0), float("inf")
@@ -89,12 +90,12 @@ def parse_model(d, ch, verbose=True):
         fl = [f] if isinstance(f, int) else list(f)
         # A width that is not a multiple of 8 (a ``Conv [nc, ...]`` layer: the one width make_divisible does not touch) can only be read
         # by a Conv or by Detect's Conv / nn.Conv2d chains: every other module moves or mixes whole 8-channel granules (hip/engine.py)
-        if i > 0 and m not in (Conv, Detect):
+        if i > 0 and m not in (Conv, DWConv, Detect):
             for j in fl:
                 if chs[j] % 8:
                     raise NotImplementedError(f"layer {i} ({mname}) reads layer {j if j >= 0 else i + j}, which is {chs[j]} channels wide: a width "
                                               f"that is not a multiple of 8 can only feed a Conv or Detect")
-        if m in (LDConv, C2f, SPPF, SPDConv) and args[0] == nc and nc % 8:
+        if m in (LDConv, C2f, SPPF, SPDConv, DWConv, DSConv) and args[0] == nc and nc % 8:
             raise NotImplementedError(f"layer {i} ({mname}) would be {nc} channels wide: only a Conv can produce a width that is not a multiple of 8")
         if m in (C2f, SPPF) and i > 0:  # their hidden widths (C2f: the chunk of cv1's output, SPPF: the pooled slices) are granules too
             c2_ = args[0] if args[0] == nc else make_divisible(min(args[0], max_channels) * width, 8)
@@ -102,15 +103,20 @@ def parse_model(d, ch, verbose=True):
             if hidden % 8:
                 raise NotImplementedError(f"layer {i} ({mname}) has a hidden width of {hidden} channels ({'its output ' + str(c2_) if m is C2f else 'its input ' + str(chs[f])}"
                                           f" halved): not a multiple of 8")
-        if m in (Conv, LDConv, C2f, SPPF, SPDConv):
+        if m in (Conv, DWConv, DSConv, LDConv, C2f, SPPF, SPDConv):
             c1, c2 = chs[f], args[0]
             if c2 != nc:
                 c2 = make_divisible(min(c2, max_channels) * width, 8)
             args = [c1, c2, *args[1:]]
+            if m is DWConv:  # the YAML row shows what the constructor would refuse: name the layer
+                depthwise_check(f"layer {i} (DWConv)", c1, c2, args[2] if len(args) > 2 else 1, args[3] if len(args) > 3 else 1, math.gcd(c1, c2),
+                                args[4] if len(args) > 4 else 1)
+            elif m is DSConv:
+                depthwise_check(f"layer {i} (DSConv.dwconv)", c1, c1, 3, 1, c1)
             if m is C2f:
                 args.insert(2, n)
                 n = 1
-            s = 2 if m is SPDConv else args[3] if (m in (Conv, LDConv) and len(args) > 3) else 1
+            s = 2 if m is SPDConv else args[3] if (m in (Conv, DWConv, LDConv) and len(args) > 3) else 1
             ds = down[f] * s
         elif m is Upsample:
             c2, ds = chs[f], down[f] / int(args[1])
@@ -199,7 +205,7 @@ class BaseModel(HipModule):
                 fl = [m.i + j if j < 0 else j for j in m.f]
                 if len(set(fl)) != len(fl) or any(j in plan for j in fl):
                     continue
-                ok = all(isinstance(self.model[j], (Conv, LDConv, C2f, SPPF, SPDConv, DySample, CARAFE, Upsample, Add, ScalSeq)) for j in fl)
+                ok = all(isinstance(self.model[j], (Conv, DSConv, LDConv, C2f, SPPF, SPDConv, DySample, CARAFE, Upsample, Add, ScalSeq)) for j in fl)
                 if ok:
                     for pos, j in enumerate(fl):
                         plan[j] = (m.i, pos)
@@ -275,7 +281,7 @@ class BaseModel(HipModule):
                 if isinstance(m, Conv) and hasattr(m, "bn"):
                     conv, bn = m.conv, m.bn
                     fused = nn.Conv2d(conv.in_channels, conv.out_channels, conv.kernel_size, conv.stride, conv.padding,
-                                      bias=True).requires_grad_(False).to(conv.weight.device)
+                                      groups=conv.groups, bias=True).requires_grad_(False).to(conv.weight.device)
                     scale = bn.weight.detach().float() / torch.sqrt(bn.eps + bn.running_var.detach().float())
                     fused.weight.copy_(conv.weight.detach().float() * scale.view(-1, 1, 1, 1))
                     fused.bias.copy_(bn.bias.detach().float() - bn.running_mean.detach().float() * scale)
@@ -431,6 +437,8 @@ class DetectionModel(BaseModel):
                 out.append(m.conv[0].out_channels)
             elif isinstance(m, SPDConv):
                 out.append(m.conv.conv.out_channels)
+            elif isinstance(m, DSConv):
+                out.append(m.pwconv.conv.out_channels)
             elif isinstance(m, (C2f, SPPF)):
                 out.append(m.cv2.conv.out_channels)
             elif isinstance(m, (Upsample, DySample, CARAFE)):

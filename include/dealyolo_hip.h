@@ -413,6 +413,32 @@ int dy_carafe(const void* x, int ldx, const void* logits, int ldl, void* y, int 
  * dy_carafe. */
 int dy_carafe_backward(const void* x, int ldx, const void* logits, int ldl, const void* dy, int lddy, void* dx, int lddx,
                        int accumulate, void* dlogits, int lddl, int n, int H, int W, int C, hipStream_t stream);
+/* ---- Depthwise convolution with channel multiplier m = c2 / c1 (reference nn/modules/conv.py:106-111 DWConv: Conv with
+ * g = math.gcd(c1, c2); :113-122 DSConv: DWConv(c1, c1, 3) then Conv(c1, c2, 1); nn.Conv2d(groups = c1), no bias, 'same' padding k / 2;
+ * BatchNorm folded by nn/tasks.py:178).  x: fp16 (n, H, W, C1) at ldx; the output (n, Ho, Wo, C1 m) with Ho = (H + 2 (k / 2) - k) / s + 1;
+ * w: the fp32 MASTER weights (C1 m, 1, k, k) -- there is no pack; output channel o reads input channel o / m.
+ * dy_dwconv_supported (host-side, no GPU needed): C1 >= 8 a multiple of 8, m in {1, 2}, k in {3, 5}, s in {1, 2}.  Every entry below:
+ * DY_ERR_ARG for anything else, a null pointer, n / H / W < 1, a pitch below its width; DY_ERR_ALIGN when a pitch is no multiple of 8
+ * or a pointer is not 16-byte aligned; nothing is launched then.  x, y and the gradients may be channel slices (pitch > width).  No
+ * allocation, no synchronisation, fixed summation orders and no atomics: two calls give the same bits (csrc/dwconv.hip lists the orders). */
+int dy_dwconv_supported(int C1, int m, int k, int s);
+/* rows of statistics partials dy_dwconv_forward writes / slabs dy_dwconv_wgrad needs for this geometry (host-side) */
+int dy_dwconv_num_partials(int n, int H, int W, int C1, int m, int k, int s);
+int dy_dwconv_wgrad_slabs(int n, int H, int W, int C1, int m, int k, int s);
+/* epi: 0 = raw fp16 output; DY_EPI_STATS = raw output + per-channel sum / sum of squares of the STORED values as rows
+ * partials[dy_dwconv_num_partials][2][C1 m] (what dy_bn_finalize / dy_bn_finalize_ld with ldp = C1 m take); DY_EPI_BIAS
+ * (| DY_EPI_SILU) = act(fp16(conv) + bias[c]) in one launch (Conv.forward_fuse, nn/modules/conv.py:57-59). */
+int dy_dwconv_forward(const void* x, int ldx, const float* w, const float* bias, void* y, int ldy, float* partials, int n, int H,
+                      int W, int C1, int m, int k, int s, int epi, hipStream_t stream);
+/* dX of the convolution (autograd of nn/modules/conv.py:52), a gather: every input pixel sums the taps that reach it (stride 2: those
+ * of its parity class) and, for m = 2, both output channels of its group, in fp32.  draw: d(raw output) fp16 at lddy; dx (n, H, W, C1)
+ * at lddx stored (accumulate = 0) or added to (1); NULL: no launch, DY_OK. */
+int dy_dwconv_input_grad(const void* draw, int lddy, const float* w, void* dx, int lddx, int accumulate, int n, int H, int W, int C1,
+                         int m, int k, int s, hipStream_t stream);
+/* dW[o][ky][kx] = sum over (n, y, x) of draw[n, y, x, o] x[n, y s + ky - k / 2, x s + kx - k / 2, o / m] in two launches: per-workgroup
+ * fp32 slabs[dy_dwconv_wgrad_slabs][C1 m k k], then their ordered reduction into dw (fp32 (C1 m, 1, k, k): stored, or added to). */
+int dy_dwconv_wgrad(const void* x, int ldx, const void* draw, int lddy, float* slabs, float* dw, int accumulate, int n, int H, int W,
+                    int C1, int m, int k, int s, hipStream_t stream);
 int dy_maxpool5(const void* x, int ldx, void* y, int ldy, void* argmax, int n, int h, int w, int C, hipStream_t stream);
 int dy_maxpool5_backward(const void* dy, int lddy, const void* argmax, void* dx, int lddx, int n, int h, int w, int C,
                          int accumulate, hipStream_t stream);
