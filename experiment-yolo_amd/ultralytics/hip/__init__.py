@@ -160,6 +160,8 @@ SIGNATURES = {
     "dy_dwconv_forward": (i32, [vp, i32, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "dy_dwconv_input_grad": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "dy_dwconv_wgrad": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "dy_adown_pool": (i32, [vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),
+    "dy_adown_pool_backward": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dy_maxpool5": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),
     "dy_maxpool5_backward": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dy_bn_group_max": (i32, []),

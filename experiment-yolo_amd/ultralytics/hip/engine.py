@@ -2071,6 +2071,45 @@ class Engine:
             self.tape.append(bwd)
         return y
 
+    # ---- ADown (reference nn/extra_modules/block.py:4685-4698) ---------------------------------------------------------
+    def adown(self, sp1: ConvSpec, sp2: ConvSpec, x: Act, out: Act | None = None, name="ADown"):
+        """``cat(cv1(avg(x)[:, :c1/2]), cv2(max_pool(avg(x)[:, c1/2:])))``: one pool launch (csrc/adown.hip) writes the averaged first
+        half into a zero-bordered even map and the pooled second half; ``cv1`` (3x3 s2) and ``cv2`` (1x1) then run as any Conv
+        (BatchNorm in training, fused after ``fuse()``) and write the two halves of ONE output buffer, so the concatenation is never
+        copied.  The arg-max map exists only when a backward pass will read it.  The pool's closure goes on the tape BEFORE the two
+        Convs': on the reversed tape it runs after them and takes their input gradients.  Frozen Convs keep their input gradients
+        when ``x`` needs one and lose their weight-gradient launches inside their own closures; an ``x`` that needs no gradient: the
+        pool leaves nothing on the tape and frozen Convs behind it nothing either."""
+        x = x.materialize() if isinstance(x, ImageAct) else self.dense(x)
+        if x.C % 16 or x.C != 2 * sp1.cin or sp2.cin != sp1.cin or sp1.cout % 8 or sp2.cout != sp1.cout or x.H < 2 or x.W < 2:
+            raise NotImplementedError(f"{name}: an input of {x.C} channels on a {x.H}x{x.W} map into cv1 {sp1.cin}->{sp1.cout}, cv2 {sp2.cin}->"
+                                      f"{sp2.cout} (supported: c1 % 16 == 0 and c2 % 16 == 0, both halves whole 8-channel granules, a map of "
+                                      f"at least 2x2)")
+        Ho, Wo, ch, co = x.H // 2, x.W // 2, x.C // 2, sp1.cout
+        a, p = self.new_act(x.N, 2 * Ho, 2 * Wo, ch), self.new_act(x.N, Ho, Wo, ch)
+        taping = self.tape is not None and x.needs_grad
+        arg = self.held((x.N * Ho * Wo * ch,), torch.uint8) if taping else None
+        self.call("dy_adown_pool", x.ptr, x.ld, a.ptr, a.ld, p.ptr, p.ld, 0 if arg is None else arg.data_ptr(), x.N, x.H, x.W, x.C)
+        if taping:
+            self._use(x)
+
+            def bwd():  # (the closure holds the arg-max tensor itself: un-recorded calls keep nothing alive otherwise)
+                assert a.grad_ready() and p.grad_ready(), f"{name}: the gradient of a pooled half is incomplete"
+                acc = x.grad_target()
+                self.call("dy_adown_pool_backward", a.gptr, a.ld, p.gptr, p.ld, arg.data_ptr(), x.gptr, x.ld, acc, x.N, x.H, x.W, x.C)
+            self.tape.append(bwd)
+        elif self.tape is not None:
+            self._no_grad(a, p)
+        y = out if out is not None else self.new_act(x.N, Ho, Wo, 2 * co)
+        assert (y.N, y.H, y.W, y.C) == (x.N, Ho, Wo, 2 * co), (name, (y.N, y.H, y.W, y.C), (x.N, Ho, Wo, 2 * co))
+        conv = lambda sp, t, o: self.conv_bn_act(sp, t, o) if sp.bn is not None else self.conv_fused(sp, t, o)  # noqa: E731
+        y1, y2 = y.sub(0, co), y.sub(co, co)
+        conv(sp1, a, y1)
+        conv(sp2, p, y2)
+        if self.tape is not None and not (y1.needs_grad or y2.needs_grad):  # (both Convs pruned their backward: so does every reader of y)
+            y.needs_grad = False
+        return y
+
     # ---- loss -----------------------------------------------------------------------------------------------------
     def zero_f32(self, t):
         self.call("dy_fill_zero", t.data_ptr(), t.numel() * t.element_size())

@@ -1,6 +1,7 @@
 """Attentional scale-sequence fusion blocks: Zoom_cat, ScalSeq, Add (drop-in for reference
 nn/extra_modules/block.py:3402-3484), SPDConv, the space-to-depth down-sampling layer (reference :2497-2507), DySample, the
-learned dynamic up-sampler (reference :3819-3892), and CARAFE, the content-aware up-sampler (reference :3898-3936)."""
+learned dynamic up-sampler (reference :3819-3892), CARAFE, the content-aware up-sampler (reference :3898-3936), and ADown, the
+YOLOv9 pooled down-sampler (reference :4685-4698)."""
 from __future__ import annotations
 
 import torch
@@ -11,7 +12,7 @@ from ...hip.engine import BN3D_EPS, BN3D_MOM
 from ...hip.runtime import HipModule
 from ..modules.conv import Conv
 
-__all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv", "DySample", "CARAFE")
+__all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv", "DySample", "CARAFE", "ADown", "adown_check")
 
 
 class Zoom_cat(HipModule):
@@ -147,3 +148,33 @@ class CARAFE(HipModule):
 
     def forward_act(self, x, out=None):
         return self.rt.eng.carafe(self.rt.spec(self.comp), self.rt.spec(self.enc), x, out)
+
+
+ADOWN_SUPPORTED = "supported: c1 % 16 == 0 and c2 % 16 == 0 (both halves whole 8-channel granules), SiLU"
+
+
+def adown_check(layer, c1, c2):
+    """The ADown widths the HIP path takes (csrc/adown.hip moves whole granules of each half).  Anything else raises, naming the
+    layer, its arguments and the supported set."""
+    if not (isinstance(c1, int) and isinstance(c2, int) and c1 >= 16 and c2 >= 16 and c1 % 16 == 0 and c2 % 16 == 0):
+        raise NotImplementedError(f"{layer}(c1={c1}, c2={c2}) is outside the HIP hot path ({ADOWN_SUPPORTED})")
+
+
+class ADown(HipModule):
+    """YOLOv9's pooled down-sampling (reference :4685-4698): a 2x2 stride-1 average, then the first half of the channels through
+    ``cv1`` (Conv 3x3 s2) and the second half through a 3x3 s2 max pool and ``cv2`` (Conv 1x1), concatenated.  The average, the
+    chunk and the max pool are one launch (csrc/adown.hip); both Convs are this package's ``Conv`` and write the two halves of one
+    output buffer.  Attribute names, ``state_dict`` keys and initialisation are the reference's."""
+
+    def __init__(self, c1, c2):
+        super().__init__()
+        adown_check("ADown", c1, c2)
+        self.c = c2 // 2
+        self.cv1 = Conv(c1 // 2, self.c, 3, 2, 1)
+        self.cv2 = Conv(c1 // 2, self.c, 1, 1, 0)
+
+    def out_hw(self, h, w):
+        return h // 2, w // 2
+
+    def forward_act(self, x, out=None):
+        return self.rt.eng.adown(self.rt.spec(self.cv1), self.rt.spec(self.cv2), x, out, name=f"ADown (layer {getattr(self, 'i', '?')})")

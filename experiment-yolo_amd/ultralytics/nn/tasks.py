@@ -20,7 +20,7 @@ import yaml
 
 from ..hip.engine import Act
 from ..hip.runtime import HipModule, Runtime
-from .extra_modules.block import CARAFE, Add, DySample, ScalSeq, SPDConv, Zoom_cat
+from .extra_modules.block import CARAFE, ADown, Add, DySample, ScalSeq, SPDConv, Zoom_cat, adown_check
 from .modules import SPPF, C2f, Concat, Conv, Detect, DSConv, DWConv, LDConv
 from .modules.conv import depthwise_check
 
@@ -45,7 +45,7 @@ class Upsample(HipModule):
 
 
 _MODULES = {"Conv": Conv, "DWConv": DWConv, "DSConv": DSConv, "LDConv": LDConv, "C2f": C2f, "SPPF": SPPF, "Concat": Concat, "nn.Upsample": Upsample,
-            "ScalSeq": ScalSeq, "Add": Add, "Zoom_cat": Zoom_cat, "Detect": Detect, "SPDConv": SPDConv, "DySample": DySample, "CARAFE": CARAFE}
+            "ScalSeq": ScalSeq, "Add": Add, "Zoom_cat": Zoom_cat, "Detect": Detect, "SPDConv": SPDConv, "DySample": DySample, "CARAFE": CARAFE, "ADown": ADown}
 
 
 def guess_model_scale(model_path):
@@ -72,7 +72,7 @@ def yaml_model_load(path):
 
 def parse_model(d, ch, verbose=True):
     """YAML dict -> (nn.Sequential, savelist, per-layer down-sampling) for the hot-path module names
-    (reference tasks.py:780-1062, branches :825-864 -- DWConv, DSConv and SPDConv are in that list (:825-843) --, :905-911, :965-967 for DySample and CARAFE,
+    (reference tasks.py:780-1062, branches :825-864 -- DWConv, DSConv, SPDConv and ADown (:840) are in that list (:825-843) --, :905-911, :965-967 for DySample and CARAFE,
     :1001-1008)."""
     nc, scales = d.get("nc"), d.get("scales")
     depth, width, max_channels = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0), float("inf")
@@ -95,7 +95,7 @@ def parse_model(d, ch, verbose=True):
                 if chs[j] % 8:
                     raise NotImplementedError(f"layer {i} ({mname}) reads layer {j if j >= 0 else i + j}, which is {chs[j]} channels wide: a width "
                                               f"that is not a multiple of 8 can only feed a Conv or Detect")
-        if m in (LDConv, C2f, SPPF, SPDConv, DWConv, DSConv) and args[0] == nc and nc % 8:
+        if m in (LDConv, C2f, SPPF, SPDConv, DWConv, DSConv, ADown) and args[0] == nc and nc % 8:
             raise NotImplementedError(f"layer {i} ({mname}) would be {nc} channels wide: only a Conv can produce a width that is not a multiple of 8")
         if m in (C2f, SPPF) and i > 0:  # their hidden widths (C2f: the chunk of cv1's output, SPPF: the pooled slices) are granules too
             c2_ = args[0] if args[0] == nc else make_divisible(min(args[0], max_channels) * width, 8)
@@ -103,7 +103,7 @@ def parse_model(d, ch, verbose=True):
             if hidden % 8:
                 raise NotImplementedError(f"layer {i} ({mname}) has a hidden width of {hidden} channels ({'its output ' + str(c2_) if m is C2f else 'its input ' + str(chs[f])}"
                                           f" halved): not a multiple of 8")
-        if m in (Conv, DWConv, DSConv, LDConv, C2f, SPPF, SPDConv):
+        if m in (Conv, DWConv, DSConv, LDConv, C2f, SPPF, SPDConv, ADown):
             c1, c2 = chs[f], args[0]
             if c2 != nc:
                 c2 = make_divisible(min(c2, max_channels) * width, 8)
@@ -113,10 +113,12 @@ def parse_model(d, ch, verbose=True):
                                 args[4] if len(args) > 4 else 1)
             elif m is DSConv:
                 depthwise_check(f"layer {i} (DSConv.dwconv)", c1, c1, 3, 1, c1)
+            elif m is ADown:
+                adown_check(f"layer {i} (ADown)", c1, c2)
             if m is C2f:
                 args.insert(2, n)
                 n = 1
-            s = 2 if m is SPDConv else args[3] if (m in (Conv, DWConv, LDConv) and len(args) > 3) else 1
+            s = 2 if m in (SPDConv, ADown) else args[3] if (m in (Conv, DWConv, LDConv) and len(args) > 3) else 1
             ds = down[f] * s
         elif m is Upsample:
             c2, ds = chs[f], down[f] / int(args[1])
@@ -205,7 +207,7 @@ class BaseModel(HipModule):
                 fl = [m.i + j if j < 0 else j for j in m.f]
                 if len(set(fl)) != len(fl) or any(j in plan for j in fl):
                     continue
-                ok = all(isinstance(self.model[j], (Conv, DSConv, LDConv, C2f, SPPF, SPDConv, DySample, CARAFE, Upsample, Add, ScalSeq)) for j in fl)
+                ok = all(isinstance(self.model[j], (Conv, DSConv, LDConv, C2f, SPPF, SPDConv, ADown, DySample, CARAFE, Upsample, Add, ScalSeq)) for j in fl)
                 if ok:
                     for pos, j in enumerate(fl):
                         plan[j] = (m.i, pos)
@@ -439,6 +441,8 @@ class DetectionModel(BaseModel):
                 out.append(m.conv.conv.out_channels)
             elif isinstance(m, DSConv):
                 out.append(m.pwconv.conv.out_channels)
+            elif isinstance(m, ADown):
+                out.append(2 * m.c)
             elif isinstance(m, (C2f, SPPF)):
                 out.append(m.cv2.conv.out_channels)
             elif isinstance(m, (Upsample, DySample, CARAFE)):

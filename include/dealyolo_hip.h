@@ -439,6 +439,25 @@ int dy_dwconv_input_grad(const void* draw, int lddy, const float* w, void* dx, i
  * fp32 slabs[dy_dwconv_wgrad_slabs][C1 m k k], then their ordered reduction into dw (fp32 (C1 m, 1, k, k): stored, or added to). */
 int dy_dwconv_wgrad(const void* x, int ldx, const void* draw, int lddy, float* slabs, float* dw, int accumulate, int n, int H, int W,
                     int C1, int m, int k, int s, hipStream_t stream);
+/* ---- The pooled front of ADown, the YOLOv9 down-sampler (reference nn/extra_modules/block.py:4685-4698: :4693
+ * ``avg_pool2d(x, 2, 1, 0, False, True)``, :4694 ``x.chunk(2, 1)``, :4696 ``max_pool2d(x2, 3, 2, 1)``; the two Convs behind it run as
+ * any Conv).  x: fp16 (n, H, W, C) at ldx, C a multiple of 16, H, W >= 2; Ho = H / 2, Wo = W / 2, c = C / 2.  ONE launch writes
+ * a (n, 2Ho, 2Wo, c) at lda: the averages of the first c channels -- fp32 ((x00 + x01) + x10) + x11, times 0.25, one fp16 rounding --
+ * with the row / column past the (H-1) x (W-1) averaged map (an even side has exactly one) written as ZERO on every launch, so that the
+ * 3x3 s2 p1 convolution behind it reads a stored zero where the reference reads padding; p (n, Ho, Wo, c) at ldp: the 3x3 s2 p1 max
+ * over the fp16 averages of the last c channels, out-of-range taps skipped; argmax (NULL in inference): the winning tap 3 ky + kx, one
+ * uint8 per element of p (dense, pitch c), the FIRST maximum in row-major (ky, kx) order as ATen has it.
+ * DY_ERR_ARG: a null pointer (argmax excepted in the forward), n < 1, H < 2, W < 2, a pitch below its width; DY_ERR_ALIGN: C % 16, a
+ * pitch that is no multiple of 8, a pointer off a 16-byte boundary; nothing is launched then.  Every operand may be a channel slice
+ * of a wider tensor: no other channel is touched.  No allocation, no synchronisation, no atomics. */
+int dy_adown_pool(const void* x, int ldx, void* a, int lda, void* p, int ldp, void* argmax, int n, int H, int W, int C,
+                  hipStream_t stream);
+/* Autograd of the three lines above, a gather over the pixels of x.  First half: dx = 0.25 x the sum of the <= 4 entries of da whose
+ * average read the pixel (the border of da is never read).  Second half: 0.25 x the sum, over those averages, of the dp of the <= 4
+ * windows whose argmax names that average.  fp32 sums in a fixed order (csrc/adown.hip), one fp16 rounding; accumulate = 1 adds to dx
+ * (one fp32 addition of the stored value, then the one rounding).  Two calls give the same bits. */
+int dy_adown_pool_backward(const void* da, int ldda, const void* dp, int lddp, const void* argmax, void* dx, int lddx, int accumulate,
+                           int n, int H, int W, int C, hipStream_t stream);
 int dy_maxpool5(const void* x, int ldx, void* y, int ldy, void* argmax, int n, int h, int w, int C, hipStream_t stream);
 int dy_maxpool5_backward(const void* dy, int lddy, const void* argmax, void* dx, int lddx, int n, int h, int w, int C,
                          int accumulate, hipStream_t stream);

@@ -1,0 +1,352 @@
+"""Generate tests/golden/adown.npz and tests/golden/ref_ckpt_adown.pt from the REFERENCE implementation: ADown (reference
+nn/extra_modules/block.py:4685-4698) on its own and inside this package's yolov8-ASF-P2P2-ADown graph.
+
+Run in the build container only (needs the reference tree, which ``_refimport`` locates):
+
+    python tests/golden/make_adown_golden.py
+
+State: ``oracle.graph.fill_state`` over the layout read off the reference module's own ``state_dict()`` (the oracle does not know
+the module and is not extended); the tests call the same function over the stored ``keys`` / ``shapes`` / ``seed``, so no weights
+are stored.  The kernels' own fixtures are seeds only: tests/adown_ref.py computes their float64 values where the tests run.
+
+adown.npz
+  ``mod/<case>/``: the reference module in train mode, fp32, N = 2: ``y``, ``gx``, ``gp/<name>`` (parameter gradients), ``buf/<name>``
+  (running statistics after the one forward) for ``x = rnd(10 seed)`` and ``gy = rnd(10 seed + 1)`` (tests/golden/cases.py), and the
+  state's ``keys`` / ``shapes`` / ``seed``.
+  ``tol/<case>/<tensor>``: measured here, not derived: the relative Frobenius error, against those fp32 values, of a float64
+  emulation of the HIP path's storage -- x, gy, the averaged map, the pooled map, every raw convolution output and its gradient,
+  every activation and gx rounded to fp16, the convolution weights rounded to fp16 (their MFMA packs).
+  ``batch/``, ``<model>/``, ``ckpt/``: as tests/golden/make_dwconv_golden.py stores them (``y_aug`` included), and ``<model>/upd_l2``:
+  the L2 norm of every trainable tensor's change over one clipped SGD-nesterov step (lr 0.01, momentum 0.9, no decay) on those gradients.
+  ``<model>/grad/<name>``: the gradients of the ten ADown convolution weights in full; ``tol/<model>/grad/<name>``: their measured l2err.
+  ``tol/<model>/{y_eval,y_aug,y_eval_fused}_{box,cls}``, ``tol/ckpt/y_eval_{box,cls}``: the eval forwards (un-fused, augmented, folded
+  in fp32 and the folded weights rounded to fp16; the checkpoint's model) under the same storage points, box rows and class rows by
+  the tests' relerr (the largest error over the largest reference value).
+  ``tol/<model>/{items,loss,grad_l2_median,grad_l2_max,grad_first,upd_l2_median,upd_l2_max}``: the same measurement for the one
+  training step of the graph: the reference's model in float64 with the image, every convolution output, every SiLU / LeakyReLU output, every sum (Bottleneck's
+  shortcut, Add, ScalSeq's tail), what ADown's two Convs read (the averaged first half, the pooled second half) and the gradients
+  that flow back through them rounded to fp16, the convolution weights rounded to fp16, Detect's final convolutions' logits left in
+  fp32 with an fp16 gradient at the loss scale (as the HIP path keeps them), against the fp32 step: the figures the test compares,
+  taken by the test's formulas.
+ref_ckpt_adown.pt: the reference's on-disk layout (engine/trainer.py:898-923) of the graph at scale ``t = [0.17, 0.25, 128]`` written
+  by the reference's classes (the narrowest widths at which every ADown row still reads whole granule pairs: 16 or 32 channels).  The
+  file is data: tensors, class paths and the YAML dict.
+"""
+import os
+import sys
+import warnings
+
+warnings.filterwarnings("ignore")
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, ROOT)
+
+os.environ["MKL_CBWR"] = "COMPATIBLE"  # as tests/conftest.py pins it
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+import yaml  # noqa: E402
+
+import _refimport  # noqa: E402
+
+_refimport.install()
+
+from ultralytics.cfg import get_cfg  # noqa: E402
+from ultralytics.nn.extra_modules.block import ADown  # noqa: E402
+from ultralytics.nn.tasks import DetectionModel  # noqa: E402
+from ultralytics.utils import DEFAULT_CFG  # noqa: E402
+from ultralytics.utils.torch_utils import initialize_weights  # noqa: E402
+
+from cases import rnd, synth_batch  # noqa: E402
+import adown_util as U  # noqa: E402
+
+assert ADown.__module__ == "ultralytics.nn.extra_modules.block" and sys.modules[ADown.__module__].__file__.startswith(_refimport.REF)
+OUR_CFG = os.path.join(ROOT, "experiment-yolo_amd", "ultralytics", "cfg", "models")
+YAML = "yolov8-ASF-P2P2-ADown.yaml"
+torch.set_num_threads(8)
+
+MODULE_SEEDS = {"ad_16_32_odd": 810, "ad_32_16_even": 811, "ad_64_128_mixed": 812}
+MODEL_SEED, BATCH_SEED, CKPT_SEED, CKPT_SCALE = 74, 60, 75, ("t", [0.17, 0.25, 128])
+BN_EPS = 1e-3   # initialize_weights
+LOSS_SCALE = 1024.0  # the tests' StepPlan(init_scale=...)
+STEP_LR, STEP_MOM = 0.01, 0.9  # the one optimizer step the updated parameters are taken after (tests/adown_util.py holds the same)
+
+
+def l2err(a, b):
+    a, b = torch.as_tensor(a).double(), torch.as_tensor(b).double()
+    return float((a - b).norm() / (b.norm() + 1e-12))
+
+
+def layout_of(module):
+    return {k: tuple(v.shape) for k, v in module.state_dict().items()}
+
+
+def put_layout(arrs, prefix, layout, seed):
+    arrs[f"{prefix}/keys"] = np.array(list(layout))
+    arrs[f"{prefix}/shapes"] = np.array([str(s) for s in layout.values()])
+    arrs[f"{prefix}/seed"] = np.int32(seed)
+
+
+class Round16(torch.autograd.Function):
+    """fp16 storage of a float64 value and of the gradient that flows back through it."""
+
+    @staticmethod
+    def forward(ctx, t):
+        return t.half().double()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.half().double()
+
+
+r16 = Round16.apply
+
+
+class GradRound16(torch.autograd.Function):
+    """An fp32 value whose GRADIENT is stored in fp16 at the step's loss scale (Detect's logits: hip/train.py, init_scale)."""
+
+    @staticmethod
+    def forward(ctx, t):
+        return t.view_as(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return (g * LOSS_SCALE).half().double() / LOSS_SCALE
+
+
+def emulate(x, gy, sd):
+    """The HIP path's storage in float64 arithmetic -> y, gx (NCHW) and the parameter gradients by state_dict name."""
+    P = {n: v.double().requires_grad_(True) for n, v in sd.items() if v.is_floating_point() and "running" not in n}
+    xa = x.half().double().requires_grad_(True)
+
+    def conv_bn(t, name, k, s):
+        z = r16(F.conv2d(t, r16(P[f"{name}conv.weight"]), None, s, k // 2))  # the raw output and d(raw), both fp16
+        z = F.batch_norm(z, None, None, P[f"{name}bn.weight"], P[f"{name}bn.bias"], True, 0.0, BN_EPS)
+        return r16(F.silu(z))
+
+    av = r16(F.avg_pool2d(xa, 2, 1, 0, False, True))  # the averaged map as stored (and the fp16 gradients of its two halves)
+    x1, x2 = av.chunk(2, 1)
+    y = torch.cat((conv_bn(x1, "cv1.", 3, 2), conv_bn(r16(F.max_pool2d(x2, 3, 2, 1)), "cv2.", 1, 1)), 1)
+    y.backward(gy.half().double())
+    return y.detach(), xa.grad.half().double(), {n: v.grad for n, v in P.items()}
+
+
+def gen_modules(arrs):
+    for name, (c1, c2, H, W) in U.MODULE_CASES.items():
+        seed = MODULE_SEEDS[name]
+        torch.manual_seed(0)
+        m = ADown(c1, c2)
+        initialize_weights(m)  # BN eps / momentum as DetectionModel.__init__ sets them
+        layout = layout_of(m)
+        sd = U.fill_state(layout, seed)
+        m.load_state_dict(sd, strict=True)
+        m.train()
+        x = rnd(10 * seed, U.BATCH, c1, H, W).requires_grad_(True)
+        y = m(x)
+        assert tuple(y.shape) == (U.BATCH, c2, H // 2, W // 2)
+        gy = rnd(10 * seed + 1, *y.shape)
+        y.backward(gy)
+        p = f"mod/{name}"
+        put_layout(arrs, p, layout, seed)
+        arrs[f"{p}/y"], arrs[f"{p}/gx"] = y.detach(), x.grad
+        for n, q in m.named_parameters():
+            arrs[f"{p}/gp/{n}"] = q.grad
+        for n, b in m.named_buffers():
+            if "running" in n:
+                arrs[f"{p}/buf/{n}"] = b.clone()
+        ey, ex, eg = emulate(x.detach(), gy, sd)
+        tol = dict(y=l2err(ey, y.detach()), gx=l2err(ex, x.grad))
+        for n, q in m.named_parameters():
+            tol[f"gp/{n}"] = l2err(eg[n], q.grad)
+        for n, v in tol.items():
+            arrs[f"tol/{name}/{n}"] = np.float64(v)
+        print(name, list(layout)[0], tuple(y.shape), "tol", {n: f"{v:.2e}" for n, v in tol.items()})
+
+
+def attach_storage(e, fused=False):
+    """The HIP path's fp16 storage points as hooks on ``e``, a float64 copy of the reference's model: every convolution's raw output
+    (``fused``: a folded Conv stores its activation only), every SiLU / LeakyReLU output, every sum (Bottleneck's shortcut, Add,
+    ScalSeq's tail), what ADown's two Convs read, the image as the stem stages it (the scaled images of augment=True too); the weights
+    of the dense convolutions rounded to fp16 (their MFMA packs); Detect's final convolutions' logits left in fp32 with an fp16
+    gradient at the loss scale."""
+    import torch.nn as nn
+    det = e.model[-1]
+    keep32 = {id(seq[-1]) for seq in list(det.cv2) + list(det.cv3)} | {id(det.dfl.conv)}
+    hook = lambda mod, inp, out: r16(out)  # noqa: E731
+    sums = ("Bottleneck", "Add", "ScalSeq")  # modules whose output is a sum (or a tail) the HIP path stores in fp16
+    for mod in e.modules():
+        if isinstance(mod, (nn.SiLU, nn.LeakyReLU)):
+            mod.inplace = False
+            mod.register_forward_hook(hook)
+        elif isinstance(mod, (nn.Conv2d, nn.Conv3d)):
+            if mod.groups == 1 and id(mod) != id(det.dfl.conv):
+                mod.weight.data = mod.weight.data.half().double()
+            if id(mod) not in keep32:
+                if not fused or isinstance(mod, nn.Conv3d):  # (a folded Conv adds its bias and applies SiLU in the convolution's launch)
+                    mod.register_forward_hook(hook)
+            elif id(mod) != id(det.dfl.conv):
+                mod.register_forward_hook(lambda mod, inp, out: GradRound16.apply(out))  # fp32 logits, fp16 gradient
+        elif type(mod).__name__ in sums:
+            mod.register_forward_hook(hook)
+        elif type(mod).__name__ == "ADown":  # what its two Convs read is stored in fp16, and so are the gradients they hand back
+            for cv in (mod.cv1, mod.cv2):
+                cv.register_forward_pre_hook(lambda mod, inp: (r16(inp[0]),))
+    e.model[0].register_forward_pre_hook(lambda mod, inp: (r16(inp[0]),))
+    return e
+
+
+def emulate_graph(m, sd0, batch):
+    """One training step of a float64 copy of ``m`` with the HIP path's fp16 storage points -> (loss, items, {name: gradient})."""
+    from copy import deepcopy
+    e = deepcopy(m)
+    e.load_state_dict(sd0)
+    attach_storage(e.double().train())
+    b64 = {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in batch.items()}
+    b64["img"] = batch["img"].half().double()  # the stem stages the image as fp16
+    loss, items = e(b64)
+    loss.backward()
+    return loss.detach(), items.detach(), {k: q.grad for k, q in e.named_parameters() if q.grad is not None}
+
+
+def emulate_eval(m, img, fused=False, augment=False):
+    """The eval forward of a float64 copy of ``m`` (its state as it stands; ``fused``: BatchNorm folded in fp32 first, as fuse() folds
+    it, then the folded weights rounded to fp16) with the HIP path's fp16 storage points."""
+    from copy import deepcopy
+    e = deepcopy(m).eval()
+    if fused:
+        e.fuse(verbose=False)
+    attach_storage(e.double(), fused)
+    with torch.no_grad():
+        return e(img.double(), augment=True)[0] if augment else e(img.double())[0]
+
+
+def relerr(a, b):
+    """tests/gpu_util.py::relerr: the largest error over the largest reference value."""
+    a, b = torch.as_tensor(a).double(), torch.as_tensor(b).double()
+    return float((a - b).abs().max() / (b.abs().max() + 1e-12))
+
+
+def put_eval_tol(arrs, prefix, got, ref):
+    """``tol/<prefix>_box`` / ``_cls``: the relerr of the emulated output's box rows and class rows, as the tests split them."""
+    arrs[f"tol/{prefix}_box"], arrs[f"tol/{prefix}_cls"] = np.float64(relerr(got[:, :4], ref[:, :4])), np.float64(relerr(got[:, 4:], ref[:, 4:]))
+    print(f"tol/{prefix} box {float(arrs[f'tol/{prefix}_box']):.2e} cls {float(arrs[f'tol/{prefix}_cls']):.2e}")
+
+
+def gen_model(arrs):
+    batch = synth_batch(BATCH_SEED, 2, 4, 6)
+    for k in ("img", "batch_idx", "cls", "bboxes"):
+        arrs[f"batch/{k}"] = batch[k]
+    name = U.MODEL
+    torch.manual_seed(0)
+    m = DetectionModel(os.path.join(OUR_CFG, name + ".yaml"), ch=3, verbose=False)
+    m.args = get_cfg(DEFAULT_CFG)
+    layout = layout_of(m)
+    assert m.yaml["nc"] == 6
+    assert [type(m.model[i]) for i in U.ADOWN_LAYERS] == [ADown] * 5
+    assert [(2 * m.model[i].cv1.conv.in_channels, 2 * m.model[i].c) for i in U.ADOWN_LAYERS] == list(U.ADOWN_WIDTHS.values())
+    put_layout(arrs, name, layout, MODEL_SEED)
+    arrs[f"{name}/n_params"] = np.int64(sum(q.numel() for q in m.parameters()))
+    arrs[f"{name}/stride"] = m.stride
+    m.load_state_dict(U.fill_state(layout, MODEL_SEED), strict=True)
+    sd0 = {k: v.clone() for k, v in m.state_dict().items()}
+    m.train()
+    loss, items = m(batch)
+    loss.backward()
+    arrs[f"{name}/loss"], arrs[f"{name}/items"] = loss.detach(), items
+    gn = {k: q.grad for k, q in m.named_parameters() if q.grad is not None}
+    arrs[f"{name}/grad_names"] = np.array(list(gn))
+    arrs[f"{name}/grad_l2"] = torch.stack([v.norm() for v in gn.values()])
+    arrs[f"{name}/grad_sum"] = torch.stack([v.sum() for v in gn.values()])
+    arrs[f"{name}/grad_first"] = gn[next(iter(gn))].clone()  # (the clip below scales the gradients in place)
+    eloss, eitems, eg = emulate_graph(m, sd0, batch)
+    for i in U.ADOWN_LAYERS:  # the gradients of the ten ADown convolution weights in full: a norm does not see a wrong direction
+        for cv in ("cv1", "cv2"):
+            k = f"model.{i}.{cv}.conv.weight"
+            arrs[f"{name}/grad/{k}"] = gn[k].clone()
+            arrs[f"tol/{name}/grad/{k}"] = np.float64(l2err(eg[k], gn[k]))
+    print(name, "tol grad/", {k.split("tol/" + name + "/grad/")[1]: f"{float(v):.2e}" for k, v in arrs.items() if k.startswith(f"tol/{name}/grad/")})
+    ref_l2 = arrs[f"{name}/grad_l2"].double()
+    rel = ((torch.stack([eg[k].norm() for k in gn]) - ref_l2).abs() / (ref_l2.abs() + 1e-3 * ref_l2.abs().max())).numpy()
+    tol = dict(items=float(((eitems - items.double()).abs() / items.double().abs()).max()), loss=float((eloss - loss.detach().double()).abs() / loss.detach().double().abs()),
+               grad_l2_median=float(np.median(rel)), grad_l2_max=float(rel.max()), grad_first=l2err(eg[next(iter(gn))], arrs[f"{name}/grad_first"]))
+    for k, v in tol.items():
+        arrs[f"tol/{name}/{k}"] = np.float64(v)
+    print(name, "tol", {k: f"{v:.2e}" for k, v in tol.items()})
+    sdm = m.state_dict()
+    rm = [k for k in sdm if k.endswith("running_mean")]
+    arrs[f"{name}/run_mean_names"] = np.array(rm)
+    arrs[f"{name}/run_mean_sum"] = torch.stack([sdm[k].sum() for k in rm])
+    arrs[f"{name}/run_var_sum"] = torch.stack([sdm[k.replace("mean", "var")].sum() for k in rm])
+    # the updated parameters: the trainer's clip at 10 (engine/trainer.py:952) and one step of the optimizer build_optimizer makes for
+    # 'SGD' (nesterov; no weight decay here), as the L2 norm of every tensor's change; the emulated step's by the same arithmetic
+    params = dict(m.named_parameters())
+    torch.nn.utils.clip_grad_norm_([params[k] for k in gn], max_norm=10.0)
+    torch.optim.SGD([params[k] for k in gn], lr=STEP_LR, momentum=STEP_MOM, nesterov=True).step()
+    arrs[f"{name}/upd_l2"] = torch.stack([(params[k].detach() - sd0[k]).norm() for k in gn])
+    coef = min(1.0, 10.0 / (float(torch.stack([eg[k].norm() for k in gn]).norm()) + 1e-6))
+    ref_u = arrs[f"{name}/upd_l2"].double()
+    relu = ((torch.stack([STEP_LR * (1 + STEP_MOM) * coef * eg[k].norm() for k in gn]) - ref_u).abs() / (ref_u.abs() + 1e-3 * ref_u.abs().max())).numpy()
+    arrs[f"tol/{name}/upd_l2_median"], arrs[f"tol/{name}/upd_l2_max"] = np.float64(np.median(relu)), np.float64(relu.max())
+    print(name, "tol upd_l2 median / max", f"{np.median(relu):.2e} {relu.max():.2e}")
+    m.load_state_dict(sd0)
+    m.eval()
+    put = lambda key, fused=False, augment=False: put_eval_tol(arrs, f"{name}/{key}", emulate_eval(m, batch["img"], fused, augment), arrs[f"{name}/{key}"])  # noqa: E731
+    with torch.no_grad():
+        arrs[f"{name}/y_eval"] = m(batch["img"])[0]
+        put("y_eval")
+        y, second = m(batch["img"], augment=True)
+        assert second is None
+        arrs[f"{name}/y_aug"] = y
+        put("y_aug", augment=True)
+        e_fused = emulate_eval(m, batch["img"], fused=True)  # (folds its own copy)
+        m.fuse(verbose=False)
+        assert m.model[1].cv1.conv.bias is not None and not hasattr(m.model[1].cv1, "bn")
+        arrs[f"{name}/y_eval_fused"] = m(batch["img"])[0]
+        put_eval_tol(arrs, f"{name}/y_eval_fused", e_fused, arrs[f"{name}/y_eval_fused"])
+    print(name, int(arrs[f"{name}/n_params"]), m.stride.tolist(), "loss", float(loss), "items", items.tolist())
+
+
+def gen_ckpt(arrs):
+    from copy import deepcopy
+    d = yaml.safe_load(open(os.path.join(OUR_CFG, YAML)))
+    d["scales"][CKPT_SCALE[0]] = CKPT_SCALE[1]
+    d["scale"] = CKPT_SCALE[0]
+    torch.manual_seed(0)
+    m = DetectionModel(d, ch=3, verbose=False)
+    layout = layout_of(m)
+    m.load_state_dict(U.fill_state(layout, CKPT_SEED), strict=True)
+    m.args = dict(get_cfg(DEFAULT_CFG).__dict__)
+    ckpt = {"epoch": 3, "best_fitness": 0.25, "model": deepcopy(m).half(), "ema": None, "updates": 57, "optimizer": None,
+            "train_args": {"imgsz": 640, "batch": 64, "model": YAML}, "date": "2026-01-01T00:00:00", "version": "8.1.9"}
+    path = os.path.join(HERE, "ref_ckpt_adown.pt")
+    torch.save(ckpt, path)
+    assert os.path.getsize(path) < 1 << 20
+    # what the checkpoint's (fp16-rounded) state computes in fp32, as a loader of either side runs it
+    m.load_state_dict({k: (v.half().float() if v.is_floating_point() else v) for k, v in m.state_dict().items()})
+    m.eval()
+    img = synth_batch(BATCH_SEED, 2, 4, 6)["img"]
+    put_layout(arrs, "ckpt", layout, CKPT_SEED)
+    arrs["ckpt/adown_channels"] = np.array([2 * m.model[i].cv1.conv.in_channels for i in U.ADOWN_LAYERS])
+    with torch.no_grad():
+        arrs["ckpt/y_eval"] = m(img)[0]
+    put_eval_tol(arrs, "ckpt/y_eval", emulate_eval(m, img), arrs["ckpt/y_eval"])
+    print(f"ref_ckpt_adown.pt  {os.path.getsize(path) / 1024:.1f} KiB, {sum(q.numel() for q in m.parameters())} parameters")
+
+
+def main():
+    arrs = {}
+    gen_modules(arrs)
+    gen_model(arrs)
+    gen_ckpt(arrs)
+    out = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in arrs.items()}
+    path = os.path.join(HERE, "adown.npz")
+    np.savez_compressed(path, **out)
+    assert os.path.getsize(path) < 1 << 20, os.path.getsize(path)
+    print(f"adown.npz  {os.path.getsize(path) / 1024:.1f} KiB  ({len(out)} arrays)")
+
+
+if __name__ == "__main__":
+    main()
