@@ -485,6 +485,14 @@ class ConvSpec:
     trainable = True  # False: every parameter of the layer is frozen (Runtime._bind_grads); its gradient views are sinks
 
 
+class FusionVec(NamedTuple):
+    """Device-side view of a Fusion layer's ``fusion_weight``: the fp32 master (a view into the flat parameter buffer), where its
+    gradient goes now (its view of the flat gradient buffer, or the sink of a frozen parameter) and whether it trains."""
+    weight: torch.Tensor
+    grad: torch.Tensor | None
+    trainable: bool
+
+
 class Engine:
     """Owns scratch memory, the tape, the recorder and the stream handle; all ops are methods."""
 
@@ -2108,6 +2116,62 @@ class Engine:
         conv(sp2, p, y2)
         if self.tape is not None and not (y1.needs_grad or y2.needs_grad):  # (both Convs pruned their backward: so does every reader of y)
             y.needs_grad = False
+        return y
+
+    # ---- Fusion, 'bifpn' mode (reference nn/extra_modules/block.py:485-488) ------------------------------------------------
+    def fusion(self, xs, pvec: FusionVec, out: Act | None = None, name="Fusion"):
+        """``sum_i f[i] x[i]`` with ``f = relu(p) / sum(relu(p))``, p read from device memory by the launch (csrc/fusion.hip): it
+        changes every step and the step is a recorded list.  An ``UpAct`` operand is read at low resolution where it lies (training
+        under UPSEG_TRAIN and the recorded inference plan alike) and receives its gradient, at full resolution, in its own gradient
+        tensor, which Upsample's closure folds; any other operand kind goes through ``dense``.  Backward: ONE pass writes every
+        needed ``dx`` (stored or added, as ``grad_target`` says) and the per-workgroup parts of the dot products, a one-workgroup
+        finish turns them into ``p``'s gradient.  A frozen ``p``: the pass without the dot products, no finish; nothing upstream and
+        ``p`` itself needing no gradient: nothing on the tape."""
+        xs = list(xs)
+        if not 2 <= len(xs) <= 3:
+            raise NotImplementedError(f"{name}: {len(xs)} operands (supported: 2 or 3 operands of one shape, a width that is a multiple of 8)")
+        self.whole8(name, *xs)
+        ops = [t if (isinstance(t, UpAct) and t._full is None) else self.dense(t) for t in xs]
+        a = ops[0]
+        if any((t.N, t.H, t.W, t.C) != (a.N, a.H, a.W, a.C) or t.st.buf.dtype != torch.float16 for t in ops):
+            raise NotImplementedError(f"{name}: operands of {[(t.N, t.C, t.H, t.W) for t in ops]} (supported: 2 or 3 operands of one shape, a "
+                                      f"width that is a multiple of 8)")
+        if pvec.weight.numel() != len(ops) or pvec.weight.dtype != torch.float32:
+            raise ValueError(f"{name}: {len(ops)} operands for a weight vector of {tuple(pvec.weight.shape)} {pvec.weight.dtype}")
+        y = out if out is not None else self.new_act(a.N, a.H, a.W, a.C)
+        assert (y.N, y.H, y.W, y.C) == (a.N, a.H, a.W, a.C), (name, (y.N, y.H, y.W, y.C), (a.N, a.H, a.W, a.C))
+        n, pptr = len(ops), pvec.weight.data_ptr()
+
+        def src(t):  # (pointer, pitch, half-resolution flag) of an operand as the kernels read it
+            return (t.src.ptr, t.src.ld, 1) if isinstance(t, UpAct) else (t.ptr, t.ld, 0)
+        fwd = [v for t in ops for v in src(t)] + [0, 0, 0] * (3 - n)
+        self._use(*ops)
+        self.call("dy_fusion_forward", *fwd, pptr, y.ptr, y.ld, n, a.N, a.H, a.W, a.C)
+        if self.tape is None:
+            return y
+        trainable = bool(pvec.trainable)
+        if not (trainable or any(t.needs_grad for t in ops)):
+            self._no_grad(y)
+            return y
+
+        def bwd():
+            assert y.grad_ready(), f"{name}: the gradient of the fused map is incomplete"
+            args = []
+            for t in ops:
+                if t.needs_grad:
+                    acc = t.grad_target()
+                    args += [*src(t), t.gptr, t.gld if isinstance(t, UpAct) else t.ld, acc]
+                else:
+                    args += [*src(t), 0, 0, 0]
+            args += [0, 0, 0, 0, 0, 0] * (3 - n)
+            ws, parts = 0, 0
+            if trainable:
+                parts = int(self.L.dy_fusion_num_partials(a.npix, a.C))
+                ws = self.scratch(("fusion_ws", self.cur_sid), 4 * 3 * parts).data_ptr()
+            self.call("dy_fusion_backward", y.gptr, y.ld, *args, pptr, ws, n, a.N, a.H, a.W, a.C)
+            if trainable:
+                self.call("dy_fusion_wgrad_finish", ws, parts, pptr, pvec.grad.data_ptr(), n, 0)
+        self.tape.append(bwd)
         return y
 
     # ---- loss -----------------------------------------------------------------------------------------------------

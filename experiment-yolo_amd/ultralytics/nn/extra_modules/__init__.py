@@ -1,3 +1,3 @@
-from .block import CARAFE, ADown, Add, DySample, ScalSeq, SPDConv, Zoom_cat
+from .block import CARAFE, ADown, Add, DySample, Fusion, ScalSeq, SPDConv, Zoom_cat
 
-__all__ = ("ADown", "CARAFE", "Add", "DySample", "ScalSeq", "SPDConv", "Zoom_cat")
+__all__ = ("ADown", "CARAFE", "Add", "DySample", "Fusion", "ScalSeq", "SPDConv", "Zoom_cat")

@@ -1,18 +1,18 @@
 """Attentional scale-sequence fusion blocks: Zoom_cat, ScalSeq, Add (drop-in for reference
 nn/extra_modules/block.py:3402-3484), SPDConv, the space-to-depth down-sampling layer (reference :2497-2507), DySample, the
-learned dynamic up-sampler (reference :3819-3892), CARAFE, the content-aware up-sampler (reference :3898-3936), and ADown, the
-YOLOv9 pooled down-sampler (reference :4685-4698)."""
+learned dynamic up-sampler (reference :3819-3892), CARAFE, the content-aware up-sampler (reference :3898-3936), ADown, the
+YOLOv9 pooled down-sampler (reference :4685-4698), and Fusion, BiFPN's weighted feature fusion (reference :453-490)."""
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
 from ...hip import DY_ACT_LEAKY, DY_ACT_NONE
-from ...hip.engine import BN3D_EPS, BN3D_MOM
+from ...hip.engine import BN3D_EPS, BN3D_MOM, FusionVec
 from ...hip.runtime import HipModule
 from ..modules.conv import Conv
 
-__all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv", "DySample", "CARAFE", "ADown", "adown_check")
+__all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv", "DySample", "CARAFE", "ADown", "adown_check", "Fusion", "fusion_check")
 
 
 class Zoom_cat(HipModule):
@@ -178,3 +178,47 @@ class ADown(HipModule):
 
     def forward_act(self, x, out=None):
         return self.rt.eng.adown(self.rt.spec(self.cv1), self.rt.spec(self.cv2), x, out, name=f"ADown (layer {getattr(self, 'i', '?')})")
+
+
+FUSION_MODES = ("weight", "adaptive", "concat", "bifpn", "SDI")  # the reference's menu (:457)
+FUSION_SUPPORTED = "supported: fusion 'bifpn' over 2 or 3 inputs of one width and map size, the width a multiple of 8; fusion 'concat'"
+
+
+def fusion_check(layer, inc_list, fusion):
+    """The Fusion forms the HIP path takes (csrc/fusion.hip for 'bifpn', the engine's Concat for 'concat').  Anything else raises,
+    naming the layer, its arguments and the supported set."""
+    inc = list(inc_list) if isinstance(inc_list, (list, tuple)) else None
+    ok = inc is not None and len(inc) >= 1 and all(isinstance(c, int) and c >= 8 and c % 8 == 0 for c in inc) and fusion in ("bifpn", "concat")
+    if ok and fusion == "bifpn":
+        ok = 2 <= len(inc) <= 3 and len(set(inc)) == 1
+    if not ok:
+        raise NotImplementedError(f"{layer}(inc_list={inc_list}, fusion={fusion!r}) is outside the HIP hot path ({FUSION_SUPPORTED})")
+
+
+class Fusion(HipModule):
+    """BiFPN's fast normalised fusion (reference :453-490, mode 'bifpn'): ``y = sum_i f[i] x[i]`` with ``f = relu(fusion_weight) /
+    sum(relu(fusion_weight))`` -- no epsilon: the reference sets ``self.epsilon = 1e-4`` and never uses it, so weights that are all
+    <= 0 give NaN (0 / 0) here as there.  ``fusion_weight`` is an fp32 vector of one value per input, initialised to ones; its
+    gradient is a dot product over whole maps (csrc/fusion.hip).  Mode 'concat' is the engine's Concat and has no parameter.
+    Constructor signature, attribute names (``fusion``, ``fusion_weight``, ``relu``, ``epsilon``) and ``state_dict`` keys are the
+    reference's, so its pickles rebuild; the other modes ('weight', 'adaptive', 'SDI') raise."""
+
+    def __init__(self, inc_list, fusion="bifpn"):
+        super().__init__()
+        if fusion not in FUSION_MODES:
+            raise ValueError(f"Fusion: fusion={fusion!r} is none of {FUSION_MODES}")
+        fusion_check("Fusion", inc_list, fusion)
+        self.fusion = fusion
+        if fusion == "bifpn":
+            self.fusion_weight = nn.Parameter(torch.ones(len(inc_list), dtype=torch.float32), requires_grad=True)
+            self.relu = nn.ReLU()
+            self.epsilon = 1e-4
+
+    def forward_act(self, xs, out=None):
+        name = f"Fusion (layer {getattr(self, 'i', '?')})"
+        if self.fusion == "concat":
+            return self.rt.eng.concat(list(xs))
+        if self.fusion != "bifpn":  # (an unpickled reference module of another mode)
+            raise NotImplementedError(f"{name}: fusion={self.fusion!r} is outside the HIP hot path ({FUSION_SUPPORTED})")
+        p = self.fusion_weight
+        return self.rt.eng.fusion(list(xs), FusionVec(p.data, self.rt.gviews.get(id(p)), p.requires_grad), out, name=name)

@@ -20,7 +20,7 @@ import yaml
 
 from ..hip.engine import Act
 from ..hip.runtime import HipModule, Runtime
-from .extra_modules.block import CARAFE, ADown, Add, DySample, ScalSeq, SPDConv, Zoom_cat, adown_check
+from .extra_modules.block import CARAFE, ADown, Add, DySample, Fusion, ScalSeq, SPDConv, Zoom_cat, adown_check, fusion_check
 from .modules import SPPF, C2f, Concat, Conv, Detect, DSConv, DWConv, LDConv
 from .modules.conv import depthwise_check
 
@@ -45,7 +45,8 @@ class Upsample(HipModule):
 
 
 _MODULES = {"Conv": Conv, "DWConv": DWConv, "DSConv": DSConv, "LDConv": LDConv, "C2f": C2f, "SPPF": SPPF, "Concat": Concat, "nn.Upsample": Upsample,
-            "ScalSeq": ScalSeq, "Add": Add, "Zoom_cat": Zoom_cat, "Detect": Detect, "SPDConv": SPDConv, "DySample": DySample, "CARAFE": CARAFE, "ADown": ADown}
+            "ScalSeq": ScalSeq, "Add": Add, "Zoom_cat": Zoom_cat, "Detect": Detect, "SPDConv": SPDConv, "DySample": DySample, "CARAFE": CARAFE, "ADown": ADown,
+            "Fusion": Fusion}
 
 
 def guess_model_scale(model_path):
@@ -72,8 +73,8 @@ def yaml_model_load(path):
 
 def parse_model(d, ch, verbose=True):
     """YAML dict -> (nn.Sequential, savelist, per-layer down-sampling) for the hot-path module names
-    (reference tasks.py:780-1062, branches :825-864 -- DWConv, DSConv, SPDConv and ADown (:840) are in that list (:825-843) --, :905-911, :965-967 for DySample and CARAFE,
-    :1001-1008)."""
+    (reference tasks.py:780-1062, branches :825-864 -- DWConv, DSConv, SPDConv and ADown (:840) are in that list (:825-843) --, :905-911, :922-925 for Fusion,
+    :965-967 for DySample and CARAFE, :1001-1008)."""
     nc, scales = d.get("nc"), d.get("scales")
     depth, width, max_channels = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0), float("inf")
     if scales:
@@ -136,6 +137,19 @@ def parse_model(d, ch, verbose=True):
             c2, ds = sum(chs[x] for x in fl), down[fl[1]]
         elif m is Add:
             c2, ds = chs[fl[-1]], down[fl[-1]]
+        elif m is Fusion:  # reference tasks.py:922-925: the mode is looked up in the YAML dict, so its NAME is a top-level key
+            if not (args and isinstance(args[0], str) and args[0] in d):
+                raise KeyError(f"layer {i} (Fusion): its argument {args[0] if args else None!r} must name a top-level key of the model YAML that "
+                               f"holds the fusion mode (e.g. 'fusion_mode: bifpn')")
+            mode = d[args[0]]
+            c1 = [chs[x] for x in fl]
+            fusion_check(f"layer {i} (Fusion)", c1, mode)
+            if mode == "bifpn" and len({down[x] for x in fl}) != 1:
+                raise NotImplementedError(f"layer {i} (Fusion)(inc_list={c1}, fusion={mode!r}) reads maps of different sizes (down-sampling "
+                                          f"{[down[x] for x in fl]}): outside the HIP hot path (supported: fusion 'bifpn' over 2 or 3 inputs of "
+                                          f"one width and map size)")
+            c2, ds = (sum(c1) if mode == "concat" else chs[fl[0]]), down[fl[0]]
+            args = [c1, mode]
         elif m is ScalSeq:
             c1 = [chs[x] for x in fl]
             c2 = make_divisible(args[0] * width, 8)
@@ -451,6 +465,9 @@ class DetectionModel(BaseModel):
                 out.append(sum(out[m.i + j if j < 0 else j] for j in m.f))
             elif isinstance(m, Add):
                 out.append(out[m.i + m.f[-1] if m.f[-1] < 0 else m.f[-1]])
+            elif isinstance(m, Fusion):
+                ws = [out[m.i + j if j < 0 else j] for j in m.f]
+                out.append(sum(ws) if m.fusion == "concat" else ws[0])
             elif isinstance(m, ScalSeq):
                 out.append(m.conv3d.out_channels)
             else:

@@ -458,6 +458,32 @@ int dy_adown_pool(const void* x, int ldx, void* a, int lda, void* p, int ldp, vo
  * (one fp32 addition of the stored value, then the one rounding).  Two calls give the same bits. */
 int dy_adown_pool_backward(const void* da, int ldda, const void* dp, int lddp, const void* argmax, void* dx, int lddx, int accumulate,
                            int n, int H, int W, int C, hipStream_t stream);
+/* ---- Fusion in 'bifpn' mode, BiFPN's fast normalised fusion (reference nn/extra_modules/block.py:453-490: :486
+ * ``fusion_weight = self.relu(self.fusion_weight.clone())``, :487 ``fusion_weight / torch.sum(fusion_weight, dim=0)``, :488 the
+ * weighted sum of the stacked operands; built by nn/tasks.py:922-925).  nops = 2 or 3 operands x_i: fp16 (n, H, W, C) at ld_i, C a
+ * multiple of 8; half_i != 0: the operand is STORED at half resolution, (n, H/2, W/2, C) (an nn.Upsample(None, 2, 'nearest') that
+ * was not executed; H and W even), and pixel (h, w) reads (h/2, w/2).  p: the fp32 parameter (nops values) in DEVICE memory, read by
+ * the launch: w = max(p, 0), s = (w0 + w1) + w2, f = w / s; NO epsilon (the reference sets self.epsilon = 1e-4 at :463 and never
+ * uses it): all weights <= 0 give NaN, as the reference's 0 / 0.  y = fp16((f0 x0 + f1 x1) + f2 x2), fp32 arithmetic, one rounding.
+ * Unused operand slots (x2 with nops = 2) are ignored.  DY_ERR_ARG: a null pointer, nops outside 2..3, n, H, W < 1, a pitch below C,
+ * an odd H or W with a half-resolution operand; DY_ERR_ALIGN: C % 8, a pitch % 8, a pointer off a 16-byte boundary (p, ws, gw: 4);
+ * nothing is launched then.  No allocation, no synchronisation, no atomics in any of the entries. */
+int dy_fusion_forward(const void* x0, int ld0, int half0, const void* x1, int ld1, int half1, const void* x2, int ld2, int half2,
+                      const float* p, void* y, int ldy, int nops, int n, int H, int W, int C, hipStream_t stream);
+/* Autograd of :486-488 in one pass over dy and the operands.  dx_i (null: the operand needs no gradient) = fp16(f_i dy), at FULL
+ * resolution at lddx_i also for a half-resolution operand (nn.Upsample's backward folds it); acc_i = 1: fp16(stored + f_i dy), one
+ * fp32 addition.  ws: fp32 [nops][dy_fusion_num_partials(n H W, C)], caller-provided: workgroup b stores its part of
+ * g_i = <dy, x_i> at ws[i * parts + b] (running fp32 sums per work item, xor-shuffle tree, the four waves in order: csrc/fusion.hip).
+ * ws = NULL: the frozen variant -- no operand is read (the x_i may be null), no dot product, the same dx bits. */
+int dy_fusion_backward(const void* dy, int lddy, const void* x0, int ld0, int half0, void* dx0, int lddx0, int acc0, const void* x1,
+                       int ld1, int half1, void* dx1, int lddx1, int acc1, const void* x2, int ld2, int half2, void* dx2, int lddx2,
+                       int acc2, const float* p, float* ws, int nops, int n, int H, int W, int C, hipStream_t stream);
+/* One workgroup: g_i = the nparts partials of ws summed in a fixed order in fp64 (as the BatchNorm statistics are), rounded to fp32;
+ * then in fp32 t = (f0 g0 + f1 g1) + f2 g2 and dL/dp_j = p_j > 0 ? (g_j - t) / s : 0, stored to gw[j] (accumulate = 0) or added to it
+ * (accumulate = 1, the convention of dy_bn_bwd_finalize's bias gradients).  gw: fusion_weight's slice of the flat gradient buffer. */
+int dy_fusion_wgrad_finish(const float* ws, int nparts, const float* p, float* gw, int nops, int accumulate, hipStream_t stream);
+/* Workgroups (= partials per dot product) of dy_fusion_backward for a map of npix pixels x C channels; < 0: DY_ERR_ARG. */
+int dy_fusion_num_partials(long npix, int C);
 int dy_maxpool5(const void* x, int ldx, void* y, int ldy, void* argmax, int n, int h, int w, int C, hipStream_t stream);
 int dy_maxpool5_backward(const void* dy, int lddy, const void* argmax, void* dx, int lddx, int n, int h, int w, int C,
                          int accumulate, hipStream_t stream);
