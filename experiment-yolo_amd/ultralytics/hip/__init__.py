@@ -167,6 +167,8 @@ SIGNATURES = {
                                  i32, i32, vp]),
     "dy_fusion_wgrad_finish": (i32, [vp, i32, vp, vp, i32, i32, vp]),
     "dy_fusion_num_partials": (i32, [i64, i32]),
+    "dy_gs_shuffle_forward": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
+    "dy_gs_shuffle_backward": (i32, [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dy_maxpool5": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),
     "dy_maxpool5_backward": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dy_bn_group_max": (i32, []),

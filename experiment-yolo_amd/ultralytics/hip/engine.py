@@ -2174,6 +2174,40 @@ class Engine:
         self.tape.append(bwd)
         return y
 
+    # ---- GSConv (reference nn/extra_modules/block.py:886-908) -----------------------------------------------------------
+    def gsconv(self, sp1: ConvSpec, sp2: ConvSpec, x: Act, out: Act | None = None, name="GSConv"):
+        """``shuffle(cat(x1, cv2(x1)))`` with ``x1 = cv1(x)``: ``cv1`` (dense 1x1 / 3x3) and the depthwise 5x5 ``cv2`` run as any Conv
+        (BatchNorm in training, fused after ``fuse()``) into tensors of their own; one launch (csrc/gsconv.hip) then writes every even
+        channel of the virtual concatenation, followed by every odd one, into ``out`` -- which may be a slice of a Concat buffer.  The
+        concatenation itself is never built.  The shuffle's closure goes on the tape AFTER the two Convs': on the reversed tape it
+        runs first, stores ``cv2``'s output gradient and gives ``x1`` its first contribution (``cv2``'s input gradient is the second,
+        added).  Pruning follows the flags the Convs left: an ``x1`` that needs no gradient (nothing upstream, ``cv1`` frozen) gets a
+        null destination; neither Conv trainable and nothing upstream: nothing on the tape."""
+        c_ = sp1.cout
+        if c_ % 8 or not sp2.dw or (sp2.cin, sp2.cout, sp2.ks, sp2.stride) != (c_, c_, 5, 1):
+            raise NotImplementedError(f"{name}: cv1 {sp1.cin}->{sp1.cout} (k={sp1.ks}, s={sp1.stride}), cv2 {sp2.cin}->{sp2.cout} (k={sp2.ks}, s={sp2.stride}, "
+                                      f"g={sp2.groups}) (supported: c2 % 16 == 0, cv2 a depthwise 5x5 of stride 1 over cv1's output)")
+        conv = lambda sp, t: self.conv_bn_act(sp, t) if sp.bn is not None else self.conv_fused(sp, t)  # noqa: E731
+        x1 = conv(sp1, x)
+        d = conv(sp2, x1)
+        y = out if out is not None else self.new_act(x1.N, x1.H, x1.W, 2 * c_)
+        assert (y.N, y.H, y.W, y.C) == (x1.N, x1.H, x1.W, 2 * c_), (name, (y.N, y.H, y.W, y.C), (x1.N, x1.H, x1.W, 2 * c_))
+        self.call("dy_gs_shuffle_forward", x1.ptr, x1.ld, d.ptr, d.ld, y.ptr, y.ld, x1.N, x1.H, x1.W, c_)
+        if self.tape is None:
+            return y
+        if not (x1.needs_grad or d.needs_grad):
+            self._no_grad(y)
+            return y
+        self._use(x1, d)
+
+        def bwd():
+            assert y.grad_ready(), f"{name}: the gradient of the shuffled map is incomplete"
+            a1 = (x1.gptr, x1.ld, x1.grad_target()) if x1.needs_grad else (0, 0, 0)
+            ad = (d.gptr, d.ld, d.grad_target()) if d.needs_grad else (0, 0, 0)
+            self.call("dy_gs_shuffle_backward", y.gptr, y.ld, *a1, *ad, x1.N, x1.H, x1.W, c_)
+        self.tape.append(bwd)
+        return y
+
     # ---- loss -----------------------------------------------------------------------------------------------------
     def zero_f32(self, t):
         self.call("dy_fill_zero", t.data_ptr(), t.numel() * t.element_size())

@@ -26,9 +26,14 @@ class Runtime:
         self.root = root
         self.eng = Engine(device)
         self.specs = {}
+        # Parameters no forward reads (``HipModule.unused_modules``: VoVGSCSP's ``res``, which the reference constructs and never
+        # calls).  The set is static -- it follows from the module classes, not from a flag -- so launch-list keys and
+        # StepPlan._check_flags never see it.  Such a module builds no ConvSpec; its parameters keep ``requires_grad`` (as in the
+        # reference, where their ``.grad`` simply stays None) but are masked like frozen ones: gradient views at the sink, their
+        # slice of the flat gradient exactly zero, no optimizer update, no weight decay, no share in the clip norm (``_flatten`` finds them).
         self._flatten()
         for m in root.modules():
-            if isinstance(m, HipModule):
+            if isinstance(m, HipModule) and id(m) not in self.unused_mods:
                 m._build_specs(self)
         self._pack_sig = None
         self.refresh_frozen()  # parameters already frozen at construction: their gradients go to the sink from the start
@@ -36,6 +41,9 @@ class Runtime:
     # ---- flat parameter / buffer storage -------------------------------------------------------------------------
     def _flatten(self):
         dev = self.eng.device
+        root = self.root
+        self.unused_mods = {id(s) for m in root.modules() if isinstance(m, HipModule) for u in m.unused_modules() for s in u.modules()}
+        self.unused_params = {id(p) for m in root.modules() if id(m) in self.unused_mods for p in m.parameters(recurse=False)}
         norm_types = tuple(v for k, v in nn.__dict__.items() if "Norm" in k and isinstance(v, type))
         groups = ([], [], [])  # bias, decayed weights, norm weights  (reference build_optimizer order g[2], g[0], g[1])
         seen = set()
@@ -92,9 +100,9 @@ class Runtime:
                 view.copy_(p.data.to(dev, torch.float32))
                 p.data = view
                 gv = self.flat_g[o:o + k].view(p.shape)
-                p.grad = gv
+                p.grad = None if id(p) in self.unused_params else gv  # (None, as in the reference: every torch.optim optimizer skips it)
                 self.gviews[id(p)] = gv
-                if not p.requires_grad:
+                if not self.updates(p):
                     self.frozen[o:o + _round(k)] = 1
                 else:
                     self.frozen[o + k:o + _round(k)] = 1  # padding never moves
@@ -136,7 +144,7 @@ class Runtime:
         need, offs = 0, {}
         for n, p in self.root.named_parameters():
             o, k = self.param_off[n], p.numel()
-            if not p.requires_grad:
+            if not self.updates(p):
                 self.frozen[o:o + _round(k)] = 1
                 offs[n] = need
                 need += _round(k)
@@ -148,12 +156,21 @@ class Runtime:
             self.eng.keep.append(self.flat_sink)  # (launch lists recorded under earlier flags may still name the old one)
         for n, p in self.root.named_parameters():
             o, k = self.param_off[n], p.numel()
-            src, o = (self.flat_g, o) if p.requires_grad else (self.flat_sink, offs[n])
+            src, o = (self.flat_g, o) if self.updates(p) else (self.flat_sink, offs[n])
             self.gviews[id(p)] = src[o:o + k].view(p.shape)
         for sp in self.specs.values():
             self._bind_grads(sp)
 
     flat_sink = None
+
+    def updates(self, p):
+        """``p`` receives a gradient and an optimizer update: it is trainable and some forward reads it."""
+        return p.requires_grad and id(p) not in self.unused_params
+
+    def unused_parameter_names(self):
+        """Names (as in ``named_parameters()`` of the root) of the parameters no forward reads, in flat-buffer order."""
+        byid = {id(p): n for n, p in self.root.named_parameters()}
+        return sorted((byid[i] for i in self.unused_params if i in byid), key=self.param_off.get)
 
     def _bind_grads(self, sp):
         """Point a ConvSpec's gradient views at where its parameters' gradients go now (``refresh_frozen``); ``sp.trainable``: it owns a
@@ -264,6 +281,10 @@ class HipModule(nn.Module):
 
     def _build_specs(self, rt):
         """Register this module's ConvSpecs with the runtime (overridden by modules that own convolutions)."""
+
+    def unused_modules(self):
+        """Sub-modules this module constructs and never calls (their parameters are state no forward reads: ``Runtime``)."""
+        return ()
 
     def _runtime(self, device):
         rt = self.__dict__.get("rt")

@@ -580,7 +580,7 @@ class StepPlan:
             from .soap import Soap, SoapHip
             views = []
             for n, p in self.model.named_parameters():
-                if p.requires_grad:
+                if rt.updates(p):  # (trainable and read by some forward: Runtime.unused_params)
                     views.append((n, rt.param_off[n], p.numel(), tuple(p.shape), rt.param_group[n]))
             self._soap_views = views
             self._soap_hip = os.environ.get("DY_SOAP_HIP", "1") != "0"  # read when the optimizer object is built

@@ -1,7 +1,8 @@
 """Attentional scale-sequence fusion blocks: Zoom_cat, ScalSeq, Add (drop-in for reference
 nn/extra_modules/block.py:3402-3484), SPDConv, the space-to-depth down-sampling layer (reference :2497-2507), DySample, the
 learned dynamic up-sampler (reference :3819-3892), CARAFE, the content-aware up-sampler (reference :3898-3936), ADown, the
-YOLOv9 pooled down-sampler (reference :4685-4698), and Fusion, BiFPN's weighted feature fusion (reference :453-490)."""
+YOLOv9 pooled down-sampler (reference :4685-4698), Fusion, BiFPN's weighted feature fusion (reference :453-490), and the slim-neck
+blocks GSConv, GSBottleneck and VoVGSCSP (reference :886-967)."""
 from __future__ import annotations
 
 import torch
@@ -12,7 +13,8 @@ from ...hip.engine import BN3D_EPS, BN3D_MOM, FusionVec
 from ...hip.runtime import HipModule
 from ..modules.conv import Conv
 
-__all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv", "DySample", "CARAFE", "ADown", "adown_check", "Fusion", "fusion_check")
+__all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv", "DySample", "CARAFE", "ADown", "adown_check", "Fusion", "fusion_check", "GSConv", "GSBottleneck", "VoVGSCSP",
+           "gsconv_check")
 
 
 class Zoom_cat(HipModule):
@@ -222,3 +224,95 @@ class Fusion(HipModule):
             raise NotImplementedError(f"{name}: fusion={self.fusion!r} is outside the HIP hot path ({FUSION_SUPPORTED})")
         p = self.fusion_weight
         return self.rt.eng.fusion(list(xs), FusionVec(p.data, self.rt.gviews.get(id(p)), p.requires_grad), out, name=name)
+
+
+GSCONV_SUPPORTED = ("supported: GSConv with c1 % 8 == 0, c2 % 16 == 0 (both halves whole 8-channel granules), (k, s) in (1, 1) | (3, 1) | (3, 2), "
+                    "p=None, g=1, d=1; VoVGSCSP / GSBottleneck with int(c2 * e) % 16 == 0; VoVGSCSP with n >= 1")
+
+
+def gsconv_check(layer, c1, c2, k=1, s=1, p=None, g=1, d=1, e=None, n=1):
+    """The slim-neck shapes the HIP path takes (csrc/gsconv.hip moves whole granules of each half of the shuffle).  ``e`` None: a
+    GSConv row; otherwise a VoVGSCSP / GSBottleneck whose hidden width ``int(c2 * e)`` is the ``c2`` of the GSConvs inside it (``n``: a
+    VoVGSCSP's bottleneck count -- without one, nothing writes the second half of the buffer ``cv3`` reads).
+    Anything else raises, naming the layer, its arguments and the supported set."""
+    ints = isinstance(c1, int) and isinstance(c2, int) and c1 >= 8 and c1 % 8 == 0
+    if e is not None:
+        if not (ints and c2 >= 16 and c2 % 8 == 0 and isinstance(e, (int, float)) and int(c2 * e) >= 16 and int(c2 * e) % 16 == 0):
+            raise NotImplementedError(f"{layer}(c1={c1}, c2={c2}, e={e}) is outside the HIP hot path ({GSCONV_SUPPORTED})")
+        if not (isinstance(n, int) and n >= 1):
+            raise NotImplementedError(f"{layer}(c1={c1}, c2={c2}, n={n}) is outside the HIP hot path ({GSCONV_SUPPORTED})")
+    elif not (ints and c2 >= 16 and c2 % 16 == 0 and (k, s) in ((1, 1), (3, 1), (3, 2)) and p is None and g == 1 and d == 1):
+        raise NotImplementedError(f"{layer}(c1={c1}, c2={c2}, k={k}, s={s}, p={p}, g={g}, d={d}) is outside the HIP hot path ({GSCONV_SUPPORTED})")
+
+
+class GSConv(HipModule):
+    """GSConv of slim-neck (reference :886-908): ``x1 = cv1(x)`` (Conv c1 -> c2 / 2, k, s), ``x2 = cat(x1, cv2(x1))`` with ``cv2`` a
+    depthwise 5x5, then the channel shuffle ``cat(x2[:, 0::2], x2[:, 1::2])`` -- one launch that reads x1 and cv2's output where they
+    lie (csrc/gsconv.hip, ``Engine.gsconv``).  ``act`` is accepted and ignored, as in the reference: both Convs always use SiLU.
+    Attribute names, ``state_dict`` keys and initialisation are the reference's."""
+
+    def __init__(self, c1, c2, k=1, s=1, p=None, g=1, d=1, act=True):
+        super().__init__()
+        gsconv_check("GSConv", c1, c2, k, s, p, g, d)
+        c_ = c2 // 2
+        self.cv1 = Conv(c1, c_, k, s, p, g, d, Conv.default_act)
+        self.cv2 = Conv(c_, c_, 5, 1, p, c_, d, Conv.default_act)
+
+    def out_hw(self, h, w):
+        return self.cv1.out_hw(h, w)
+
+    def forward_act(self, x, out=None):
+        return self.rt.eng.gsconv(self.rt.spec(self.cv1), self.rt.spec(self.cv2), x, out, name=f"GSConv (layer {getattr(self, 'i', '?')})")
+
+
+class GSBottleneck(HipModule):
+    """GS bottleneck (reference :923-935): ``conv_lighting(x) + shortcut(x)`` with ``conv_lighting`` two GSConvs (1x1, then 3x3) and
+    ``shortcut`` a 1x1 Conv without activation.  ``k`` and ``s`` are accepted and ignored, as in the reference.  The sum is one
+    ``Engine.add`` launch, which may write a slice of the caller's buffer."""
+
+    def __init__(self, c1, c2, k=3, s=1, e=0.5):
+        super().__init__()
+        gsconv_check("GSBottleneck", c1, c2, e=e)
+        c_ = int(c2 * e)
+        self.conv_lighting = nn.Sequential(GSConv(c1, c_, 1, 1), GSConv(c_, c2, 3, 1, act=False))
+        self.shortcut = Conv(c1, c2, 1, 1, act=False)
+
+    def forward_act(self, x, out=None):
+        a = self.conv_lighting[1].forward_act(self.conv_lighting[0].forward_act(x))
+        return self.rt.eng.add([a, self.shortcut.forward_act(x)], out)
+
+
+class VoVGSCSP(HipModule):
+    """VoV-GSCSP (reference :953-967): ``cv3(cat(cv2(x), gsb(cv1(x))))`` with ``gsb`` a chain of ``n`` GSBottlenecks at e = 1.
+    ``shortcut`` and ``g`` are accepted and ignored.  ``res``, a 3x3 Conv, is constructed and NEVER called, exactly as in the
+    reference: its parameters and BatchNorm buffers are in ``state_dict()`` and in the parameter count, and nothing ever reads or
+    changes them (``unused_modules``: no ConvSpec, no pack, no launch, no gradient, no optimizer update).  ``cv2`` and the last
+    bottleneck's sum write the two halves of one buffer that ``cv3`` reads, or stay where they are as the members of a segment table."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        gsconv_check("VoVGSCSP", c1, c2, e=e, n=n)
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c1, c_, 1, 1)
+        self.gsb = nn.Sequential(*(GSBottleneck(c_, c_, e=1.0) for _ in range(n)))
+        self.res = Conv(c_, c_, 3, 1, act=False)
+        self.cv3 = Conv(2 * c_, c2, 1)
+
+    def unused_modules(self):
+        return (self.res,)
+
+    def forward_act(self, x, out=None):
+        from ...hip.engine import PLANAR, SegAct
+        eng, c_, n = self.rt.eng, self.cv1.conv.out_channels, len(self.gsb)
+        x1 = self.cv1.forward_act(x)
+        if PLANAR:
+            y = self.cv2.forward_act(x)
+            for b in self.gsb:
+                x1 = b.forward_act(x1)
+            return self.cv3.forward_act(SegAct([y, x1]), out)
+        cat = eng.new_storage(x1.N, x1.H, x1.W, 2 * c_)
+        self.cv2.forward_act(x, cat.act(0, c_))
+        for j, b in enumerate(self.gsb):
+            x1 = b.forward_act(x1, cat.act(c_, c_) if j == n - 1 else None)
+        return self.cv3.forward_act(cat.act(), out)

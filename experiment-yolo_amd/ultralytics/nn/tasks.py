@@ -20,7 +20,8 @@ import yaml
 
 from ..hip.engine import Act
 from ..hip.runtime import HipModule, Runtime
-from .extra_modules.block import CARAFE, ADown, Add, DySample, Fusion, ScalSeq, SPDConv, Zoom_cat, adown_check, fusion_check
+from .extra_modules.block import (CARAFE, ADown, Add, DySample, Fusion, GSConv, ScalSeq, SPDConv, VoVGSCSP, Zoom_cat, adown_check, fusion_check,
+                                  gsconv_check)
 from .modules import SPPF, C2f, Concat, Conv, Detect, DSConv, DWConv, LDConv
 from .modules.conv import depthwise_check
 
@@ -46,7 +47,7 @@ class Upsample(HipModule):
 
 _MODULES = {"Conv": Conv, "DWConv": DWConv, "DSConv": DSConv, "LDConv": LDConv, "C2f": C2f, "SPPF": SPPF, "Concat": Concat, "nn.Upsample": Upsample,
             "ScalSeq": ScalSeq, "Add": Add, "Zoom_cat": Zoom_cat, "Detect": Detect, "SPDConv": SPDConv, "DySample": DySample, "CARAFE": CARAFE, "ADown": ADown,
-            "Fusion": Fusion}
+            "Fusion": Fusion, "GSConv": GSConv, "VoVGSCSP": VoVGSCSP}
 
 
 def guess_model_scale(model_path):
@@ -73,7 +74,7 @@ def yaml_model_load(path):
 
 def parse_model(d, ch, verbose=True):
     """YAML dict -> (nn.Sequential, savelist, per-layer down-sampling) for the hot-path module names
-    (reference tasks.py:780-1062, branches :825-864 -- DWConv, DSConv, SPDConv and ADown (:840) are in that list (:825-843) --, :905-911, :922-925 for Fusion,
+    (reference tasks.py:780-1062, branches :825-864 -- DWConv, DSConv, SPDConv, ADown (:840), GSConv and VoVGSCSP (:828; repeats :874-875) are in that list (:825-843) --, :905-911, :922-925 for Fusion,
     :965-967 for DySample and CARAFE, :1001-1008)."""
     nc, scales = d.get("nc"), d.get("scales")
     depth, width, max_channels = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0), float("inf")
@@ -96,7 +97,7 @@ def parse_model(d, ch, verbose=True):
                 if chs[j] % 8:
                     raise NotImplementedError(f"layer {i} ({mname}) reads layer {j if j >= 0 else i + j}, which is {chs[j]} channels wide: a width "
                                               f"that is not a multiple of 8 can only feed a Conv or Detect")
-        if m in (LDConv, C2f, SPPF, SPDConv, DWConv, DSConv, ADown) and args[0] == nc and nc % 8:
+        if m in (LDConv, C2f, SPPF, SPDConv, DWConv, DSConv, ADown, GSConv, VoVGSCSP) and args[0] == nc and nc % 8:
             raise NotImplementedError(f"layer {i} ({mname}) would be {nc} channels wide: only a Conv can produce a width that is not a multiple of 8")
         if m in (C2f, SPPF) and i > 0:  # their hidden widths (C2f: the chunk of cv1's output, SPPF: the pooled slices) are granules too
             c2_ = args[0] if args[0] == nc else make_divisible(min(args[0], max_channels) * width, 8)
@@ -104,7 +105,7 @@ def parse_model(d, ch, verbose=True):
             if hidden % 8:
                 raise NotImplementedError(f"layer {i} ({mname}) has a hidden width of {hidden} channels ({'its output ' + str(c2_) if m is C2f else 'its input ' + str(chs[f])}"
                                           f" halved): not a multiple of 8")
-        if m in (Conv, DWConv, DSConv, LDConv, C2f, SPPF, SPDConv, ADown):
+        if m in (Conv, DWConv, DSConv, LDConv, C2f, SPPF, SPDConv, ADown, GSConv, VoVGSCSP):
             c1, c2 = chs[f], args[0]
             if c2 != nc:
                 c2 = make_divisible(min(c2, max_channels) * width, 8)
@@ -116,10 +117,14 @@ def parse_model(d, ch, verbose=True):
                 depthwise_check(f"layer {i} (DSConv.dwconv)", c1, c1, 3, 1, c1)
             elif m is ADown:
                 adown_check(f"layer {i} (ADown)", c1, c2)
-            if m is C2f:
+            elif m is GSConv:
+                gsconv_check(f"layer {i} (GSConv)", *args[:7])
+            elif m is VoVGSCSP:  # (args[2], when present, is ``shortcut``: n is inserted below)
+                gsconv_check(f"layer {i} (VoVGSCSP)", c1, c2, e=args[4] if len(args) > 4 else 0.5)
+            if m in (C2f, VoVGSCSP):
                 args.insert(2, n)
                 n = 1
-            s = 2 if m in (SPDConv, ADown) else args[3] if (m in (Conv, DWConv, LDConv) and len(args) > 3) else 1
+            s = 2 if m in (SPDConv, ADown) else args[3] if (m in (Conv, DWConv, LDConv, GSConv) and len(args) > 3) else 1
             ds = down[f] * s
         elif m is Upsample:
             c2, ds = chs[f], down[f] / int(args[1])
@@ -221,7 +226,8 @@ class BaseModel(HipModule):
                 fl = [m.i + j if j < 0 else j for j in m.f]
                 if len(set(fl)) != len(fl) or any(j in plan for j in fl):
                     continue
-                ok = all(isinstance(self.model[j], (Conv, DSConv, LDConv, C2f, SPPF, SPDConv, ADown, DySample, CARAFE, Upsample, Add, ScalSeq)) for j in fl)
+                ok = all(isinstance(self.model[j], (Conv, DSConv, LDConv, C2f, SPPF, SPDConv, ADown, GSConv, VoVGSCSP, DySample, CARAFE, Upsample, Add, ScalSeq))
+                         for j in fl)
                 if ok:
                     for pos, j in enumerate(fl):
                         plan[j] = (m.i, pos)
@@ -435,9 +441,14 @@ class DetectionModel(BaseModel):
         forward is exactly zero (bias-free convs, BN beta = 0, SiLU(0) = 0; LDConv samples zeros whatever its offsets; ScalSeq's
         Conv3d adds its bias, a per-channel constant that its BatchNorm3d removes again), so its only lasting effect is on the
         BN buffers: running_var = 0.9 * 1 + 0.1 * 0, num_batches_tracked = 1, and running_mean = 0.1 * conv3d.bias in ScalSeq.
+        A module that no forward calls (``unused_modules``: VoVGSCSP's ``res``) keeps running_var = 1, running_mean = 0,
+        num_batches_tracked = 0, as in the reference.
         Strides are static here; this reproduces the buffers a freshly built reference model starts training from (checked
         against the reference in tests/test_host_logic.py; the reference's rounding noise of ~1e-8 in a few means is not)."""
+        unrun = {id(s) for mod in self.modules() if isinstance(mod, HipModule) for u in mod.unused_modules() for s in u.modules()}
         for mod in self.modules():
+            if id(mod) in unrun:  # (a module no forward calls, VoVGSCSP.res: the probe never ran its BatchNorm either)
+                continue
             if isinstance(mod, (nn.BatchNorm2d, nn.BatchNorm3d)):
                 mod.running_var.fill_(0.9)
                 mod.num_batches_tracked.fill_(1)
@@ -457,6 +468,10 @@ class DetectionModel(BaseModel):
                 out.append(m.pwconv.conv.out_channels)
             elif isinstance(m, ADown):
                 out.append(2 * m.c)
+            elif isinstance(m, GSConv):
+                out.append(2 * m.cv1.conv.out_channels)
+            elif isinstance(m, VoVGSCSP):
+                out.append(m.cv3.conv.out_channels)
             elif isinstance(m, (C2f, SPPF)):
                 out.append(m.cv2.conv.out_channels)
             elif isinstance(m, (Upsample, DySample, CARAFE)):

@@ -484,6 +484,22 @@ int dy_fusion_backward(const void* dy, int lddy, const void* x0, int ld0, int ha
 int dy_fusion_wgrad_finish(const float* ws, int nparts, const float* p, float* gw, int nops, int accumulate, hipStream_t stream);
 /* Workgroups (= partials per dot product) of dy_fusion_backward for a map of npix pixels x C channels; < 0: DY_ERR_ARG. */
 int dy_fusion_num_partials(long npix, int C);
+/* ---- GSConv's channel shuffle (reference nn/extra_modules/block.py:896-908: ``x2 = cat(x1, cv2(x1))``, then the reshape / permute /
+ * reshape / cat chain, which is exactly ``cat(x2[:, 0::2], x2[:, 1::2])``: every even channel of x2, then every odd one).  x1, d: fp16
+ * (n, H, W, c_) at ld1 / ldd, the two halves of x2, which is never built; y: fp16 (n, H, W, 2 c_) at ldy; y[j] = x2[2 j],
+ * y[c_ + j] = x2[2 j + 1].  c_ a multiple of 8.  One work item per (pixel, 8 output channels): the two 16-byte granules of x2 that hold them are loaded,
+ * one 16-byte granule is stored; consecutive lanes store consecutive granules.
+ * DY_ERR_ARG: a null pointer, n / H / W < 1, c_ < 8, a pitch below its width (c_, c_, 2 c_); DY_ERR_ALIGN: c_ % 8, a pitch that is no
+ * multiple of 8, a pointer off a 16-byte boundary; nothing is launched then.  Every operand may be a channel slice of a wider tensor:
+ * no other channel is touched.  No allocation, no synchronisation, no atomics; 64-bit offsets. */
+int dy_gs_shuffle_forward(const void* x1, int ld1, const void* d, int ldd, void* y, int ldy, int n, int H, int W, int c_,
+                          hipStream_t stream);
+/* Its autograd, the inverse interleave: the gradient of x2[2 j] is dy[j], of x2[2 j + 1] dy[c_ + j]; the first c_ channels of that go to
+ * dx1, the rest to dd.  A destination whose flag (acc1 / accd) is set receives fp16(old + v), one fp32 addition; otherwise it is
+ * stored.  A null destination is skipped (its pitch is not looked at); both null: DY_OK, nothing launched.  Errors as above (dy is
+ * required).  Two calls give the same bits. */
+int dy_gs_shuffle_backward(const void* dy, int ldy, void* dx1, int ld1, int acc1, void* dd, int ldd, int accd, int n, int H, int W,
+                           int c_, hipStream_t stream);
 int dy_maxpool5(const void* x, int ldx, void* y, int ldy, void* argmax, int n, int h, int w, int C, hipStream_t stream);
 int dy_maxpool5_backward(const void* dy, int lddy, const void* argmax, void* dx, int lddx, int n, int h, int w, int C,
                          int accumulate, hipStream_t stream);
