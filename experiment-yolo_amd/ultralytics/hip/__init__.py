@@ -167,6 +167,9 @@ SIGNATURES = {
                                  i32, i32, vp]),
     "dy_fusion_wgrad_finish": (i32, [vp, i32, vp, vp, i32, i32, vp]),
     "dy_fusion_num_partials": (i32, [i64, i32]),
+    "dy_simam_forward": (i32, [vp, i32, vp, i32, vp, vp, f32, i32, i32, i32, i32, vp]),
+    "dy_simam_backward": (i32, [vp, i32, vp, i32, vp, vp, i32, i32, vp, i32, i32, i32, i32, vp]),
+    "dy_simam_num_partials": (i32, [i64, i32]),
     "dy_gs_shuffle_forward": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, vp]),
     "dy_gs_shuffle_backward": (i32, [vp, i32, vp, i32, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
     "dy_maxpool5": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, vp]),

@@ -2208,6 +2208,35 @@ class Engine:
         self.tape.append(bwd)
         return y
 
+    # ---- SimAM (reference nn/extra_modules/attention.py:69-77) -----------------------------------------------------------
+    def simam(self, x: Act, e_lambda=1e-4, out: Act | None = None, name="SimAM"):
+        """``x * sigmoid(d^2 / (4 (sum(d^2) / (H W - 1) + e_lambda)) + 0.5)``, ``d = x - mean(x)`` per image and channel over the
+        plane (csrc/simam.hip: a statistics launch and an apply launch each way, fp64 partials in stream-ordered scratch).  The
+        fp32 (mu, 1 / D) of every plane, which the backward reads, is a step-local buffer (the arena's under a StepPlan).  No
+        parameters: the backward is recorded only when ``x`` needs a gradient; otherwise the output is marked instead."""
+        self.whole8(name, x)
+        x = self.dense(x)
+        if x.st.buf.dtype != torch.float16:
+            raise NotImplementedError(f"{name}: an input of {x.st.buf.dtype} (supported: fp16 maps, a width that is a multiple of 8)")
+        y = out if out is not None else self.new_act(x.N, x.H, x.W, x.C)
+        assert (y.N, y.H, y.W, y.C) == (x.N, x.H, x.W, x.C), (name, (y.N, y.H, y.W, y.C), (x.N, x.H, x.W, x.C))
+        parts = int(self.L.dy_simam_num_partials(x.H * x.W, x.C))
+        if parts < 1:
+            raise RuntimeError(f"{name}: dy_simam_num_partials({x.H * x.W}, {x.C}) = {parts}")
+        wsbytes = 8 * x.N * parts * 2 * x.C
+        stats = self.held((x.N * 2 * x.C,), torch.float32)
+        self._use(x)
+        self.call("dy_simam_forward", x.ptr, x.ld, y.ptr, y.ld, stats.data_ptr(), self.scratch(("simam_ws", self.cur_sid), wsbytes).data_ptr(),
+                  float(e_lambda), x.N, x.H, x.W, x.C)
+
+        def bwd():
+            assert y.grad_ready(), f"{name}: the gradient of the attended map is incomplete"
+            acc = x.grad_target()
+            self.call("dy_simam_backward", y.gptr, y.ld, x.ptr, x.ld, stats.data_ptr(), x.gptr, x.ld, acc,
+                      self.scratch(("simam_ws", self.cur_sid), wsbytes).data_ptr(), x.N, x.H, x.W, x.C)
+        self._record(self._live(None, x), y, bwd)
+        return y
+
     # ---- loss -----------------------------------------------------------------------------------------------------
     def zero_f32(self, t):
         self.call("dy_fill_zero", t.data_ptr(), t.numel() * t.element_size())

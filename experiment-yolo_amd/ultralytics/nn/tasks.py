@@ -20,6 +20,7 @@ import yaml
 
 from ..hip.engine import Act
 from ..hip.runtime import HipModule, Runtime
+from .extra_modules.attention import SimAM
 from .extra_modules.block import (CARAFE, ADown, Add, DySample, Fusion, GSConv, ScalSeq, SPDConv, VoVGSCSP, Zoom_cat, adown_check, fusion_check,
                                   gsconv_check)
 from .modules import SPPF, C2f, Concat, Conv, Detect, DSConv, DWConv, LDConv
@@ -47,7 +48,7 @@ class Upsample(HipModule):
 
 _MODULES = {"Conv": Conv, "DWConv": DWConv, "DSConv": DSConv, "LDConv": LDConv, "C2f": C2f, "SPPF": SPPF, "Concat": Concat, "nn.Upsample": Upsample,
             "ScalSeq": ScalSeq, "Add": Add, "Zoom_cat": Zoom_cat, "Detect": Detect, "SPDConv": SPDConv, "DySample": DySample, "CARAFE": CARAFE, "ADown": ADown,
-            "Fusion": Fusion, "GSConv": GSConv, "VoVGSCSP": VoVGSCSP}
+            "Fusion": Fusion, "GSConv": GSConv, "VoVGSCSP": VoVGSCSP, "SimAM": SimAM}
 
 
 def guess_model_scale(model_path):
@@ -75,7 +76,7 @@ def yaml_model_load(path):
 def parse_model(d, ch, verbose=True):
     """YAML dict -> (nn.Sequential, savelist, per-layer down-sampling) for the hot-path module names
     (reference tasks.py:780-1062, branches :825-864 -- DWConv, DSConv, SPDConv, ADown (:840), GSConv and VoVGSCSP (:828; repeats :874-875) are in that list (:825-843) --, :905-911, :922-925 for Fusion,
-    :965-967 for DySample and CARAFE, :1001-1008)."""
+    :965-967 for DySample and CARAFE, :969-970 for SimAM, :1001-1008)."""
     nc, scales = d.get("nc"), d.get("scales")
     depth, width, max_channels = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0), float("inf")
     if scales:
@@ -136,6 +137,9 @@ def parse_model(d, ch, verbose=True):
             c2 = chs[f]
             args = [c2, *args]
             ds = down[f] / 2
+        elif m is SimAM:  # reference tasks.py:969-970: ``c2 = ch[f]``, the args passed through (SpatialGroupEnhance shares the branch
+            c2, ds = chs[f], down[f]  # there and is no hot-path name here); a width off the 8-channel granule was refused above
+            args = [float(a) if isinstance(a, str) else a for a in args]  # YAML 1.1 reads ``1e-4`` as a string; the reference evals it (:817)
         elif m is Concat:
             c2, ds = sum(chs[x] for x in fl), down[fl[0]]
         elif m is Zoom_cat:
@@ -474,7 +478,7 @@ class DetectionModel(BaseModel):
                 out.append(m.cv3.conv.out_channels)
             elif isinstance(m, (C2f, SPPF)):
                 out.append(m.cv2.conv.out_channels)
-            elif isinstance(m, (Upsample, DySample, CARAFE)):
+            elif isinstance(m, (Upsample, DySample, CARAFE, SimAM)):
                 out.append(out[m.i + m.f if m.f < 0 else m.f])
             elif isinstance(m, (Concat, Zoom_cat)):
                 out.append(sum(out[m.i + j if j < 0 else j] for j in m.f))

@@ -484,6 +484,30 @@ int dy_fusion_backward(const void* dy, int lddy, const void* x0, int ld0, int ha
 int dy_fusion_wgrad_finish(const float* ws, int nparts, const float* p, float* gw, int nops, int accumulate, hipStream_t stream);
 /* Workgroups (= partials per dot product) of dy_fusion_backward for a map of npix pixels x C channels; < 0: DY_ERR_ARG. */
 int dy_fusion_num_partials(long npix, int C);
+/* ---- SimAM, parameter-free attention (reference nn/extra_modules/attention.py:53-77: :72 ``n = w * h - 1``, :74 the squared
+ * deviation from the plane mean, :75 ``/ (4 * (sum / n + e_lambda)) + 0.5``, :77 ``x * sigmoid(y)``; built by nn/tasks.py:969-970).
+ * Per image and channel over the M = H W values of the plane: mu = mean(x), d = x - mu, S = sum(d^2), D = 4 (S / (M - 1) + e_lambda),
+ * y = x sigmoid(d^2 / D + 0.5).  x, y: fp16 (n, H, W, C) at ldx / ldy, C a multiple of 8 (an operand may be a channel slice of a
+ * wider tensor; nothing outside its C channels is read or written).  Two launches: plane sums of x and x^2 through fp64
+ * accumulators (exact for fp16 inputs, so a mean far above the spread needs no second pass), one fp64 partial per
+ * (image, pixel run, sum, channel) in ws; then every workgroup folds its image's partials in a fixed order and applies.  stats: fp32
+ * [n][2][C], written here -- mu and 1 / D per (image, channel) -- and read by dy_simam_backward.  ws: fp64
+ * [n][dy_simam_num_partials(H W, C)][2][C], caller-provided scratch.  All other arithmetic is fp32 (csrc/simam.hip states it), one
+ * fp16 rounding of y.  A plane of ONE pixel gives 0 / 0: its y is NaN, as the reference's; nothing guards it.  DY_ERR_ARG: a null
+ * pointer, n, H, W < 1, C < 8 or not a multiple of 8, a pitch below C; DY_ERR_ALIGN: a pitch % 8, a pointer off a 16-byte boundary
+ * (ws: 8); nothing is launched then.  No allocation, no synchronisation, no atomics: two calls give the same bits. */
+int dy_simam_forward(const void* x, int ldx, void* y, int ldy, float* stats, double* ws, float e_lambda, int n, int H, int W, int C,
+                     hipStream_t stream);
+/* Autograd of :72-77 through the plane's mean and variance.  With g = dy, a recomputed from x and stats (never stored),
+ * q = g x a (1 - a), T = sum(q d^2), U = sum(q d) over the plane:  dx = g a + (2 d / D) (q - 4 T / ((M - 1) D)) - 2 U / (M D).
+ * Two launches as the forward: T and U through fp64 accumulators into ws (same size as the forward's), then the fold and dx,
+ * stored (accumulate = 0) or added to what is there (accumulate = 1: one fp32 addition of the stored value, then the one
+ * rounding).  Reads dy and x twice: 4 reads + 1 write (+ 1 read when accumulating) of the map. */
+int dy_simam_backward(const void* dy, int lddy, const void* x, int ldx, const float* stats, void* dx, int lddx, int accumulate,
+                      double* ws, int n, int H, int W, int C, hipStream_t stream);
+/* Pixel runs (= fp64 partials per plane sum) per image of the two entries above for planes of M = H W pixels x C channels;
+ * < 0: DY_ERR_ARG. */
+int dy_simam_num_partials(long M, int C);
 /* ---- GSConv's channel shuffle (reference nn/extra_modules/block.py:896-908: ``x2 = cat(x1, cv2(x1))``, then the reshape / permute /
  * reshape / cat chain, which is exactly ``cat(x2[:, 0::2], x2[:, 1::2])``: every even channel of x2, then every odd one).  x1, d: fp16
  * (n, H, W, c_) at ld1 / ldd, the two halves of x2, which is never built; y: fp16 (n, H, W, 2 c_) at ldy; y[j] = x2[2 j],

@@ -28,7 +28,7 @@ CFG_DIR = os.path.join(ROOT, "experiment-yolo_amd", "ultralytics", "cfg", "model
 MAIN = "yolov8n-ASF-P2P2"
 MODELS = ["yolov8n-p2", "yolov8n-ASF", "yolov8n-ASF-P2", MAIN, "yolov8n-ASF-P2P2-SPD", "yolov8n-ASF-P2P2-DySample",
           "yolov8n-ASF-P2P2-CARAFE", "yolov8n-ASF-P2P2-DW", "yolov8n-ASF-P2P2-ADown", "yolov8n-ASF-P2P2-BiFPN",
-          "yolov8n-ASF-P2P2-SlimNeck", "yolov8n-LD-P2", "yolov8n-LD-P2-SPD"]
+          "yolov8n-ASF-P2P2-SlimNeck", "yolov8n-ASF-P2P2-SimAM", "yolov8n-LD-P2", "yolov8n-LD-P2-SPD"]
 SWITCHES = ["DY_BN_ACC=0", "DY_BN_WGRAD=0", "DY_BN_RES=0", "DY_BIAS_WGRAD=0", "DY_BN_GROUP=0", "DY_HEAD_ROWS=0",
             "DY_HEAD_CLS=0 DY_HEAD_APPLY=0", "DY_WGRAD_DGRAD=0", "DY_PLANAR=0", "DY_PLANAR_CV1=0", "DY_PLANAR_CV1=0 DY_SIDE_WGRAD=1",
             "DY_SIDE_WGRAD=1", "DY_HEAD_STREAMS=1", "DY_UPSEG_TRAIN=0", "DY_STEM_DIRECT=0", "DY_BN_DGRED=1 DY_BN_DGRED_MAXC=32"]
