@@ -754,6 +754,13 @@ class Engine:
         """An activation of LOGICAL width C (any C >= 1) in a storage of its own, round8(C) wide."""
         return self.new_storage(N, H, W, round8(C)).act(0, C)
 
+    def out_act(self, out, N, H, W, C, name=None):
+        """Where an op writes: ``out`` (a slice of the caller's buffer), which must have the op's output shape, or a new activation."""
+        if out is None:
+            return self.new_act(N, H, W, C)
+        assert (out.N, out.H, out.W, out.C) == (N, H, W, C), (name, (out.N, out.H, out.W, out.C), (N, H, W, C))
+        return out
+
     @staticmethod
     def whole8(op, *xs):
         """Only Conv / nn.Conv2d consume an activation whose width is not a multiple of 8 (they read its zero pad lanes as
@@ -1106,8 +1113,7 @@ class Engine:
         x = self._dw_input(spec, x, out, res)
         Ho, Wo = self.out_hw(spec, x)
         raw = self.new_act(x.N, Ho, Wo, spec.cout)
-        y = out if out is not None else self.new_act(x.N, Ho, Wo, spec.cout)
-        assert (y.N, y.H, y.W, y.C) == (x.N, Ho, Wo, spec.cout), (spec.name, (y.N, y.H, y.W, y.C), (x.N, Ho, Wo, spec.cout))
+        y = self.out_act(out, x.N, Ho, Wo, spec.cout, spec.name)
         live = self._live(spec, x)
         if live:
             self._use(x)
@@ -1501,6 +1507,10 @@ class Engine:
             self.call("dy_add", y.ptr, y.ld, res.ptr, res.ld, 0, 0, y.ptr, y.ld, y.npix, y.C)
         return y
 
+    def conv(self, spec: ConvSpec, x: Act, out: Act | None = None):
+        """A ``Conv`` inside a composite op (CARAFE, ADown, GSConv): with its BatchNorm, or fused after ``fuse()``."""
+        return self.conv_bn_act(spec, x, out) if spec.bn is not None else self.conv_fused(spec, x, out)
+
     def conv_bias(self, spec: ConvSpec, x: Act, y_ptr, ldy, f32out=True, dy_ptr_fn=None, out_hw=None, rows_level=None):
         """Plain conv + bias (Detect's final nn.Conv2d 1x1, reference nn/modules/head.py:38-42).  ``dy_ptr_fn`` returns
         (ptr, ld) of the fp16 gradient w.r.t. the output at backward time.  ``rows_level``: this is the box branch of detection
@@ -1712,8 +1722,7 @@ class Engine:
         x = self.dense(x)
         if x.H % 2 or x.W % 2 or x.H < 2 or x.W < 2:
             raise ValueError(f"space-to-depth needs an even map, got {x.H}x{x.W}")
-        y = out if out is not None else self.new_act(x.N, x.H // 2, x.W // 2, 4 * x.C)
-        assert (y.N, y.H, y.W, y.C) == (x.N, x.H // 2, x.W // 2, 4 * x.C)
+        y = self.out_act(out, x.N, x.H // 2, x.W // 2, 4 * x.C, "SPDConv")
         self._use(x)
         self.call("dy_space_to_depth", x.ptr, x.ld, y.ptr, y.ld, x.N, x.H, x.W, x.C, 0, 0)
 
@@ -1777,30 +1786,28 @@ class Engine:
         assert len(xs) <= 3
         self._use(*xs)
         self.call("dy_add", a.ptr, a.ld, b.ptr, b.ld, 0 if c is None else c.ptr, 0 if c is None else c.ld, y.ptr, y.ld, a.npix, a.C)
-        if self.tape is not None and not self._live(None, *xs):
-            self._no_grad(y)
-        elif self.tape is not None:
-            def bwd():
-                shared = False
-                for t in xs:
-                    if not t.needs_grad:
-                        continue
-                    if (ADD_ALIAS and not shared and t.st.gbuf is None and not t.st.gwritten and t.c0 == 0 and t.C == t.st.C
-                            and y.c0 == 0 and y.C == y.st.C and y.st.gbuf is not None and tuple(t.st.buf.shape) == tuple(y.st.buf.shape)
-                            and self._uses.get(id(t.st)) == {(t.c0, t.C): 1}):
-                        # d(sum)/d(operand) is the identity: an operand whose ONLY forward use was this sum, and which has no gradient
-                        # yet, takes the sum's gradient buffer as its own instead of a copy of it (nothing writes y's gradient after
-                        # this point, and nothing else will write t's).  One operand per sum: two sharers could see each other's writers.
-                        t.st.gbuf = y.st.gbuf
-                        t.grad_target()
-                        shared = True
-                        continue
-                    acc = t.grad_target()
-                    if acc:
-                        self.call("dy_add", t.gptr, t.ld, y.gptr, y.ld, 0, 0, t.gptr, t.ld, t.npix, t.C)
-                    else:
-                        self.call("dy_copy_slice", y.gptr, y.ld, t.gptr, t.ld, t.npix, t.C)
-            self.tape.append(bwd)
+
+        def bwd():
+            shared = False
+            for t in xs:
+                if not t.needs_grad:
+                    continue
+                if (ADD_ALIAS and not shared and t.st.gbuf is None and not t.st.gwritten and t.c0 == 0 and t.C == t.st.C
+                        and y.c0 == 0 and y.C == y.st.C and y.st.gbuf is not None and tuple(t.st.buf.shape) == tuple(y.st.buf.shape)
+                        and self._uses.get(id(t.st)) == {(t.c0, t.C): 1}):
+                    # d(sum)/d(operand) is the identity: an operand whose ONLY forward use was this sum, and which has no gradient
+                    # yet, takes the sum's gradient buffer as its own instead of a copy of it (nothing writes y's gradient after
+                    # this point, and nothing else will write t's).  One operand per sum: two sharers could see each other's writers.
+                    t.st.gbuf = y.st.gbuf
+                    t.grad_target()
+                    shared = True
+                    continue
+                acc = t.grad_target()
+                if acc:
+                    self.call("dy_add", t.gptr, t.ld, y.gptr, y.ld, 0, 0, t.gptr, t.ld, t.npix, t.C)
+                else:
+                    self.call("dy_copy_slice", y.gptr, y.ld, t.gptr, t.ld, t.npix, t.C)
+        self._record(self._live(None, *xs), y, bwd)
         return y
 
     def concat(self, xs, out_storage=None):
@@ -1836,21 +1843,19 @@ class Engine:
                 self.call("dy_copy_slice", t.ptr, t.ld, y.ptr + 2 * off, y.ld, t.npix, t.C)
             parts.append((t, off))
             off += t.C
-        if self.tape is not None and not self._live(None, *xs):
-            self._no_grad(y)
-        elif self.tape is not None:
-            def bwd():
-                for t, o in parts:
-                    if not t.needs_grad:
-                        continue
-                    acc = t.grad_target()
-                    gsrc = y.gptr + 2 * o
-                    gl = t.gld if isinstance(t, UpAct) else t.ld  # (an UpAct's gradient tensor is full-resolution, of its own pitch)
-                    if acc:
-                        self.call("dy_add", t.gptr, gl, gsrc, y.ld, 0, 0, t.gptr, gl, t.npix, t.C)
-                    else:
-                        self.call("dy_copy_slice", gsrc, y.ld, t.gptr, gl, t.npix, t.C)
-            self.tape.append(bwd)
+
+        def bwd():
+            for t, o in parts:
+                if not t.needs_grad:
+                    continue
+                acc = t.grad_target()
+                gsrc = y.gptr + 2 * o
+                gl = t.gld if isinstance(t, UpAct) else t.ld  # (an UpAct's gradient tensor is full-resolution, of its own pitch)
+                if acc:
+                    self.call("dy_add", t.gptr, gl, gsrc, y.ld, 0, 0, t.gptr, gl, t.npix, t.C)
+                else:
+                    self.call("dy_copy_slice", gsrc, y.ld, t.gptr, gl, t.npix, t.C)
+        self._record(self._live(None, *xs), y, bwd)
         return y
 
     def zoom_cat(self, xs, out: Act | None = None):
@@ -1865,23 +1870,21 @@ class Engine:
         self.call("dy_zoom_pool", l.ptr, l.ld, yl.ptr, yl.ld, l.N, m.H, m.W, l.C)
         self.call("dy_copy_slice", m.ptr, m.ld, ym.ptr, ym.ld, m.npix, m.C)
         self.call("dy_upsample2x", s.ptr, s.ld, ys.ptr, ys.ld, s.N, s.H, s.W, s.C, 0, 0)
-        if self.tape is not None and not self._live(None, l, m, s):
-            self._no_grad(y)
-        elif self.tape is not None:
-            def bwd():
-                if l.needs_grad:
-                    acc = l.grad_target()
-                    self.call("dy_zoom_pool_backward", l.ptr, l.ld, yl.gptr, yl.ld, l.gptr, l.ld, l.N, m.H, m.W, l.C, acc)
-                if m.needs_grad:
-                    acc = m.grad_target()
-                    if acc:
-                        self.call("dy_add", m.gptr, m.ld, ym.gptr, ym.ld, 0, 0, m.gptr, m.ld, m.npix, m.C)
-                    else:
-                        self.call("dy_copy_slice", ym.gptr, ym.ld, m.gptr, m.ld, m.npix, m.C)
-                if s.needs_grad:
-                    acc = s.grad_target()
-                    self.call("dy_upsample2x", ys.gptr, ys.ld, s.gptr, s.ld, s.N, s.H, s.W, s.C, 1, acc)
-            self.tape.append(bwd)
+
+        def bwd():
+            if l.needs_grad:
+                acc = l.grad_target()
+                self.call("dy_zoom_pool_backward", l.ptr, l.ld, yl.gptr, yl.ld, l.gptr, l.ld, l.N, m.H, m.W, l.C, acc)
+            if m.needs_grad:
+                acc = m.grad_target()
+                if acc:
+                    self.call("dy_add", m.gptr, m.ld, ym.gptr, ym.ld, 0, 0, m.gptr, m.ld, m.npix, m.C)
+                else:
+                    self.call("dy_copy_slice", ym.gptr, ym.ld, m.gptr, m.ld, m.npix, m.C)
+            if s.needs_grad:
+                acc = s.grad_target()
+                self.call("dy_upsample2x", ys.gptr, ys.ld, s.gptr, s.ld, s.N, s.H, s.W, s.C, 1, acc)
+        self._record(self._live(None, l, m, s), y, bwd)
         return y
 
     # ---- ScalSeq (reference nn/extra_modules/block.py:3426-3443) --------------------------------------------------
@@ -1923,23 +1926,21 @@ class Engine:
                 self._use(res)
         self.call("dy_scalseq_tail", raws[0].ptr, raws[0].ld, raws[1].ptr, raws[1].ld, raws[2].ptr, raws[2].ld,
                   0 if res is None else res.ptr, 0 if res is None else res.ld, y.ptr, y.ld, coef.data_ptr(), N, H, W, Cc)
-        if self.tape is not None and not live:
-            self._no_grad(y)
-        elif self.tape is not None:
-            def bwd():
-                if res is not None and res.needs_grad:  # d(sum)/d(res) = identity, as in Engine.add
-                    if (ADD_ALIAS and res.st.gbuf is None and not res.st.gwritten and res.c0 == 0 and res.C == res.st.C and y.c0 == 0
-                            and y.C == y.st.C and y.st.gbuf is not None and tuple(res.st.buf.shape) == tuple(y.st.buf.shape)):
-                        # res has no gradient yet: it takes y's gradient buffer as its own.  Every writer of y's gradient has run, its
-                        # one reader (the ScalSeq backward below) runs before anything can be added to res's gradient.
-                        res.st.gbuf = y.st.gbuf
-                        res.grad_target()
-                    elif res.grad_target():
-                        self.call("dy_add", res.gptr, res.ld, y.gptr, y.ld, 0, 0, res.gptr, res.ld, res.npix, res.C)
-                    else:
-                        self.call("dy_copy_slice", y.gptr, y.ld, res.gptr, res.ld, res.npix, res.C)
-                self._scalseq_bwd(conv3d, coef, bwdcoef, gbn, ps, raws, y)
-            self.tape.append(bwd)
+
+        def bwd():
+            if res is not None and res.needs_grad:  # d(sum)/d(res) = identity, as in Engine.add
+                if (ADD_ALIAS and res.st.gbuf is None and not res.st.gwritten and res.c0 == 0 and res.C == res.st.C and y.c0 == 0
+                        and y.C == y.st.C and y.st.gbuf is not None and tuple(res.st.buf.shape) == tuple(y.st.buf.shape)):
+                    # res has no gradient yet: it takes y's gradient buffer as its own.  Every writer of y's gradient has run, its
+                    # one reader (the ScalSeq backward below) runs before anything can be added to res's gradient.
+                    res.st.gbuf = y.st.gbuf
+                    res.grad_target()
+                elif res.grad_target():
+                    self.call("dy_add", res.gptr, res.ld, y.gptr, y.ld, 0, 0, res.gptr, res.ld, res.npix, res.C)
+                else:
+                    self.call("dy_copy_slice", y.gptr, y.ld, res.gptr, res.ld, res.npix, res.C)
+            self._scalseq_bwd(conv3d, coef, bwdcoef, gbn, ps, raws, y)
+        self._record(live, y, bwd)
         return y
 
     def _scalseq_bwd(self, conv3d, coef, bwdcoef, gbn, ps, raws, y):
@@ -1977,27 +1978,25 @@ class Engine:
         xo = self.new_act(x.N, h, w, Np * x.C)
         self.call("dy_ldconv_sample", x.ptr, x.ld, off.data_ptr(), 2 * Np, pn_i32.data_ptr(), xo.ptr, xo.ld, x.N, x.H, x.W, h, w,
                   x.C, Np, stride)
-        if self.tape is not None and not live:
-            self._no_grad(xo)
-        elif self.tape is not None:
-            def bwd():
-                assert xo.grad_ready()
-                if not x.needs_grad:  # stem: offset gradient only
-                    self.call("dy_ldconv_sample_backward", x.ptr, x.ld, off.data_ptr(), 2 * Np, pn_i32.data_ptr(), xo.gptr, xo.ld,
-                              0, doff.data_ptr(), doff.shape[-1], x.N, x.H, x.W, h, w, x.C, Np, stride)
-                    return
-                dx32 = self.scratch("ld_dx32", x.npix * x.C * 4)  # touched only when the offsets outgrow the gather radius
-                acc = x.grad_target()
-                if os.environ.get("DY_LD_SCATTER", "0") == "1":  # measurement switch: the atomic path on its own
-                    self.call("dy_fill_zero", dx32.data_ptr(), x.npix * x.C * 4)
-                    self.call("dy_ldconv_sample_backward", x.ptr, x.ld, off.data_ptr(), 2 * Np, pn_i32.data_ptr(), xo.gptr, xo.ld,
-                              dx32.data_ptr(), doff.data_ptr(), doff.shape[-1], x.N, x.H, x.W, h, w, x.C, Np, stride)
-                    self.call("dy_f32_to_f16_add", dx32.data_ptr(), x.gptr, x.ld, x.npix, x.C, acc)
-                    return
-                self.call("dy_ldconv_sample_backward_gather", x.ptr, x.ld, off.data_ptr(), 2 * Np, pn_i32.data_ptr(), xo.gptr, xo.ld,
-                          x.gptr, x.ld, acc, dx32.data_ptr(), doff.data_ptr(), doff.shape[-1], self.scratch("ld_maxabs", 16).data_ptr(),
-                          int(os.environ.get("DY_LD_RMAX", "2")), x.N, x.H, x.W, h, w, x.C, Np, stride)
-            self.tape.append(bwd)
+
+        def bwd():
+            assert xo.grad_ready()
+            if not x.needs_grad:  # stem: offset gradient only
+                self.call("dy_ldconv_sample_backward", x.ptr, x.ld, off.data_ptr(), 2 * Np, pn_i32.data_ptr(), xo.gptr, xo.ld,
+                          0, doff.data_ptr(), doff.shape[-1], x.N, x.H, x.W, h, w, x.C, Np, stride)
+                return
+            dx32 = self.scratch("ld_dx32", x.npix * x.C * 4)  # touched only when the offsets outgrow the gather radius
+            acc = x.grad_target()
+            if os.environ.get("DY_LD_SCATTER", "0") == "1":  # measurement switch: the atomic path on its own
+                self.call("dy_fill_zero", dx32.data_ptr(), x.npix * x.C * 4)
+                self.call("dy_ldconv_sample_backward", x.ptr, x.ld, off.data_ptr(), 2 * Np, pn_i32.data_ptr(), xo.gptr, xo.ld,
+                          dx32.data_ptr(), doff.data_ptr(), doff.shape[-1], x.N, x.H, x.W, h, w, x.C, Np, stride)
+                self.call("dy_f32_to_f16_add", dx32.data_ptr(), x.gptr, x.ld, x.npix, x.C, acc)
+                return
+            self.call("dy_ldconv_sample_backward_gather", x.ptr, x.ld, off.data_ptr(), 2 * Np, pn_i32.data_ptr(), xo.gptr, xo.ld,
+                      x.gptr, x.ld, acc, dx32.data_ptr(), doff.data_ptr(), doff.shape[-1], self.scratch("ld_maxabs", 16).data_ptr(),
+                      int(os.environ.get("DY_LD_RMAX", "2")), x.N, x.H, x.W, h, w, x.C, Np, stride)
+        self._record(live, xo, bwd)
         return self.conv_bn_act(sp_c, xo, out)
 
     # ---- DySample (reference nn/extra_modules/block.py:3819-3892, style 'lp') ---------------------------------------
@@ -2027,24 +2026,21 @@ class Engine:
                 self.tape.append(lambda: self._input_grad(sp_off, x, doff.data_ptr(), nch, x.H, x.W))
         if live:
             self._use(x)  # the sampler's backward writes x's gradient too
-        y = out if out is not None else self.new_act(x.N, s * x.H, s * x.W, x.C)
-        assert (y.N, y.H, y.W, y.C) == (x.N, s * x.H, s * x.W, x.C)
+        y = self.out_act(out, x.N, s * x.H, s * x.W, x.C, "DySample")
         self.call("dy_dysample", x.ptr, x.ld, off.data_ptr(), nch, y.ptr, y.ld, x.N, x.H, x.W, x.C, G, s)
-        if self.tape is not None and not live:
-            self._no_grad(y)
-        elif self.tape is not None:
-            def bwd():
-                assert y.grad_ready()
-                if not x.needs_grad:  # offset gradient only
-                    self.call("dy_dysample_backward", x.ptr, x.ld, off.data_ptr(), nch, y.gptr, y.ld, 0, 0, 0, 0, doff.data_ptr(), nch,
-                              0, 0, x.N, x.H, x.W, x.C, G, s)
-                    return
-                dx32 = self.scratch("ld_dx32", x.npix * x.C * 4)  # touched only when the offsets outgrow the gather radius
-                acc = x.grad_target()
-                self.call("dy_dysample_backward", x.ptr, x.ld, off.data_ptr(), nch, y.gptr, y.ld, x.gptr, x.ld, acc, dx32.data_ptr(),
-                          doff.data_ptr(), nch, self.scratch("ld_maxabs", 16).data_ptr(), int(os.environ.get("DY_DS_RMAX", "2")),
-                          x.N, x.H, x.W, x.C, G, s)
-            self.tape.append(bwd)
+
+        def bwd():
+            assert y.grad_ready()
+            if not x.needs_grad:  # offset gradient only
+                self.call("dy_dysample_backward", x.ptr, x.ld, off.data_ptr(), nch, y.gptr, y.ld, 0, 0, 0, 0, doff.data_ptr(), nch,
+                          0, 0, x.N, x.H, x.W, x.C, G, s)
+                return
+            dx32 = self.scratch("ld_dx32", x.npix * x.C * 4)  # touched only when the offsets outgrow the gather radius
+            acc = x.grad_target()
+            self.call("dy_dysample_backward", x.ptr, x.ld, off.data_ptr(), nch, y.gptr, y.ld, x.gptr, x.ld, acc, dx32.data_ptr(),
+                      doff.data_ptr(), nch, self.scratch("ld_maxabs", 16).data_ptr(), int(os.environ.get("DY_DS_RMAX", "2")),
+                      x.N, x.H, x.W, x.C, G, s)
+        self._record(live, y, bwd)
         return y
 
     # ---- CARAFE (reference nn/extra_modules/block.py:3898-3936, k_up 5, scale 2) ------------------------------------
@@ -2059,24 +2055,20 @@ class Engine:
         if not self.L.dy_carafe_supported(x.C, 5, 2) or sp_enc.cout != 100:
             raise NotImplementedError(f"CARAFE on {x.C} channels with a {sp_enc.cout}-channel encoder: the reassembly takes k_up 5, scale 2 "
                                       "(100 encoder channels) and channels that are a multiple of 8")
-        conv = lambda sp, t: self.conv_bn_act(sp, t) if sp.bn is not None else self.conv_fused(sp, t)  # noqa: E731
-        lg = conv(sp_enc, conv(sp_comp, x))  # (read by this op only, lane by lane: no whole8)
+        lg = self.conv(sp_enc, self.conv(sp_comp, x))  # (read by this op only, lane by lane: no whole8)
         live = self.tape is None or lg.needs_grad or x.needs_grad
         if live:
             self._use(x, lg)
-        y = out if out is not None else self.new_act(x.N, 2 * x.H, 2 * x.W, x.C)
-        assert (y.N, y.H, y.W, y.C) == (x.N, 2 * x.H, 2 * x.W, x.C)
+        y = self.out_act(out, x.N, 2 * x.H, 2 * x.W, x.C, "CARAFE")
         self.call("dy_carafe", x.ptr, x.ld, lg.ptr, lg.ld, y.ptr, y.ld, x.N, x.H, x.W, x.C)
-        if self.tape is not None and not live:
-            self._no_grad(y)
-        elif self.tape is not None:
-            def bwd():
-                assert y.grad_ready()
-                assert lg.grad_target() == 0, "CARAFE is the only reader of its logits"
-                dx, ldx, acc = (x.gptr, x.ld, x.grad_target()) if x.needs_grad else (0, 0, 0)
-                self.call("dy_carafe_backward", x.ptr, x.ld, lg.ptr, lg.ld, y.gptr, y.ld, dx, ldx, acc, lg.gptr, lg.ld,
-                          x.N, x.H, x.W, x.C)
-            self.tape.append(bwd)
+
+        def bwd():
+            assert y.grad_ready()
+            assert lg.grad_target() == 0, "CARAFE is the only reader of its logits"
+            dx, ldx, acc = (x.gptr, x.ld, x.grad_target()) if x.needs_grad else (0, 0, 0)
+            self.call("dy_carafe_backward", x.ptr, x.ld, lg.ptr, lg.ld, y.gptr, y.ld, dx, ldx, acc, lg.gptr, lg.ld,
+                      x.N, x.H, x.W, x.C)
+        self._record(live, y, bwd)
         return y
 
     # ---- ADown (reference nn/extra_modules/block.py:4685-4698) ---------------------------------------------------------
@@ -2108,12 +2100,10 @@ class Engine:
             self.tape.append(bwd)
         elif self.tape is not None:
             self._no_grad(a, p)
-        y = out if out is not None else self.new_act(x.N, Ho, Wo, 2 * co)
-        assert (y.N, y.H, y.W, y.C) == (x.N, Ho, Wo, 2 * co), (name, (y.N, y.H, y.W, y.C), (x.N, Ho, Wo, 2 * co))
-        conv = lambda sp, t, o: self.conv_bn_act(sp, t, o) if sp.bn is not None else self.conv_fused(sp, t, o)  # noqa: E731
+        y = self.out_act(out, x.N, Ho, Wo, 2 * co, name)
         y1, y2 = y.sub(0, co), y.sub(co, co)
-        conv(sp1, a, y1)
-        conv(sp2, p, y2)
+        self.conv(sp1, a, y1)
+        self.conv(sp2, p, y2)
         if self.tape is not None and not (y1.needs_grad or y2.needs_grad):  # (both Convs pruned their backward: so does every reader of y)
             y.needs_grad = False
         return y
@@ -2138,8 +2128,7 @@ class Engine:
                                       f"width that is a multiple of 8)")
         if pvec.weight.numel() != len(ops) or pvec.weight.dtype != torch.float32:
             raise ValueError(f"{name}: {len(ops)} operands for a weight vector of {tuple(pvec.weight.shape)} {pvec.weight.dtype}")
-        y = out if out is not None else self.new_act(a.N, a.H, a.W, a.C)
-        assert (y.N, y.H, y.W, y.C) == (a.N, a.H, a.W, a.C), (name, (y.N, y.H, y.W, y.C), (a.N, a.H, a.W, a.C))
+        y = self.out_act(out, a.N, a.H, a.W, a.C, name)
         n, pptr = len(ops), pvec.weight.data_ptr()
 
         def src(t):  # (pointer, pitch, half-resolution flag) of an operand as the kernels read it
@@ -2147,12 +2136,7 @@ class Engine:
         fwd = [v for t in ops for v in src(t)] + [0, 0, 0] * (3 - n)
         self._use(*ops)
         self.call("dy_fusion_forward", *fwd, pptr, y.ptr, y.ld, n, a.N, a.H, a.W, a.C)
-        if self.tape is None:
-            return y
         trainable = bool(pvec.trainable)
-        if not (trainable or any(t.needs_grad for t in ops)):
-            self._no_grad(y)
-            return y
 
         def bwd():
             assert y.grad_ready(), f"{name}: the gradient of the fused map is incomplete"
@@ -2171,7 +2155,7 @@ class Engine:
             self.call("dy_fusion_backward", y.gptr, y.ld, *args, pptr, ws, n, a.N, a.H, a.W, a.C)
             if trainable:
                 self.call("dy_fusion_wgrad_finish", ws, parts, pptr, pvec.grad.data_ptr(), n, 0)
-        self.tape.append(bwd)
+        self._record(trainable or any(t.needs_grad for t in ops), y, bwd)
         return y
 
     # ---- GSConv (reference nn/extra_modules/block.py:886-908) -----------------------------------------------------------
@@ -2187,11 +2171,9 @@ class Engine:
         if c_ % 8 or not sp2.dw or (sp2.cin, sp2.cout, sp2.ks, sp2.stride) != (c_, c_, 5, 1):
             raise NotImplementedError(f"{name}: cv1 {sp1.cin}->{sp1.cout} (k={sp1.ks}, s={sp1.stride}), cv2 {sp2.cin}->{sp2.cout} (k={sp2.ks}, s={sp2.stride}, "
                                       f"g={sp2.groups}) (supported: c2 % 16 == 0, cv2 a depthwise 5x5 of stride 1 over cv1's output)")
-        conv = lambda sp, t: self.conv_bn_act(sp, t) if sp.bn is not None else self.conv_fused(sp, t)  # noqa: E731
-        x1 = conv(sp1, x)
-        d = conv(sp2, x1)
-        y = out if out is not None else self.new_act(x1.N, x1.H, x1.W, 2 * c_)
-        assert (y.N, y.H, y.W, y.C) == (x1.N, x1.H, x1.W, 2 * c_), (name, (y.N, y.H, y.W, y.C), (x1.N, x1.H, x1.W, 2 * c_))
+        x1 = self.conv(sp1, x)
+        d = self.conv(sp2, x1)
+        y = self.out_act(out, x1.N, x1.H, x1.W, 2 * c_, name)
         self.call("dy_gs_shuffle_forward", x1.ptr, x1.ld, d.ptr, d.ld, y.ptr, y.ld, x1.N, x1.H, x1.W, c_)
         if self.tape is None:
             return y
@@ -2218,8 +2200,7 @@ class Engine:
         x = self.dense(x)
         if x.st.buf.dtype != torch.float16:
             raise NotImplementedError(f"{name}: an input of {x.st.buf.dtype} (supported: fp16 maps, a width that is a multiple of 8)")
-        y = out if out is not None else self.new_act(x.N, x.H, x.W, x.C)
-        assert (y.N, y.H, y.W, y.C) == (x.N, x.H, x.W, x.C), (name, (y.N, y.H, y.W, y.C), (x.N, x.H, x.W, x.C))
+        y = self.out_act(out, x.N, x.H, x.W, x.C, name)
         parts = int(self.L.dy_simam_num_partials(x.H * x.W, x.C))
         if parts < 1:
             raise RuntimeError(f"{name}: dy_simam_num_partials({x.H * x.W}, {x.C}) = {parts}")

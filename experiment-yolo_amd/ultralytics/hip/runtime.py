@@ -278,6 +278,16 @@ class HipModule(nn.Module):
     """Base of every hot-path module: ``forward`` accepts public tensors or engine Acts and routes to ``forward_act``."""
 
     rt: Runtime | None = None
+    # what the model graph (nn/tasks.py) asks a module class, instead of keeping lists of classes
+    ragged_in = False      # may read a width that is not a multiple of 8 (every other module moves whole 8-channel granules)
+    ragged_out = False     # may produce such a width (a ``[nc, ...]`` row: the one width make_divisible does not touch)
+    repeat_is_arg = False  # the row's repeat count is a constructor argument: the row builds ONE module
+    concat_dst = False     # ``forward_act(x, out)`` can write into a channel slice of a Concat's buffer
+
+    @classmethod
+    def yaml_row(cls, row):
+        """One model-YAML row (nn/rows.py ``Row``) -> (constructor arguments, output width, down-sampling of the output)."""
+        raise NotImplementedError(f"{row.layer}: {cls.__name__} does not say how it reads a model YAML row")
 
     def _build_specs(self, rt):
         """Register this module's ConvSpecs with the runtime (overridden by modules that own convolutions)."""

@@ -5,6 +5,7 @@ from __future__ import annotations
 import torch.nn as nn
 
 from ...hip.runtime import HipModule
+from ..rows import same_width_row
 
 __all__ = ("SimAM",)
 
@@ -15,6 +16,11 @@ class SimAM(HipModule):
     keys; constructor signature, attribute names (``activaton`` as the reference spells it, ``e_lambda``), ``__repr__`` and
     ``get_module_name`` are the reference's, so its pickles rebuild.  A 1x1 map has ``n = 0``: the output is NaN (0 / 0), here as
     there."""
+    # (concat_dst stays False although ``forward_act`` takes ``out``: that is how the Concat plan was before the attribute, not a decision)
+
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:969-970; YAML 1.1 reads ``1e-4`` as a string, the reference evals it (:817)
+        return same_width_row(row, [float(a) if isinstance(a, str) else a for a in row.args])
 
     def __init__(self, e_lambda=1e-4):
         super().__init__()

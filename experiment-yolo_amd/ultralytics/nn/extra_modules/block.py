@@ -12,6 +12,7 @@ from ...hip import DY_ACT_LEAKY, DY_ACT_NONE
 from ...hip.engine import BN3D_EPS, BN3D_MOM, FusionVec
 from ...hip.runtime import HipModule
 from ..modules.conv import Conv
+from ..rows import conv_row, same_width_row
 
 __all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv", "DySample", "CARAFE", "ADown", "adown_check", "Fusion", "fusion_check", "GSConv", "GSBottleneck", "VoVGSCSP",
            "gsconv_check")
@@ -20,6 +21,10 @@ __all__ = ("Zoom_cat", "ScalSeq", "Add", "SPDConv", "DySample", "CARAFE", "ADown
 class Zoom_cat(HipModule):
     """cat(maxpool+avgpool of the fine map, middle map, nearest-upsampled coarse map) (reference :3402-3412)."""
 
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:1001-1002; the output has the middle map's size
+        return row.args, sum(row.chs), row.down[1]
+
     def forward_act(self, xs, out=None):
         return self.rt.eng.zoom_cat(list(xs), out)
 
@@ -27,6 +32,12 @@ class Zoom_cat(HipModule):
 class ScalSeq(HipModule):
     """Scale-sequence feature fusion (reference :3414-3443): 1x1 Convs on the two coarser levels, nearest resize to the
     finest, Conv3d(1x1x1)+BatchNorm3d+LeakyReLU(0.1) over the 3-deep stack, max over depth."""
+    concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:1005-1008: the width is scaled without the max_channels cap
+        c2 = row.scaled(row.args[0], capped=False)
+        return [row.chs, c2], c2, row.down[0]
 
     def __init__(self, inc, channel):
         super().__init__()
@@ -60,6 +71,11 @@ class ScalSeq(HipModule):
 
 class Add(HipModule):
     """Element-wise sum of the inputs (reference :3479-3484)."""
+    concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:1003-1004
+        return row.args, row.chs[-1], row.down[-1]
 
     def forward_act(self, xs, out=None):
         return self.rt.eng.add(list(xs), out)
@@ -70,6 +86,11 @@ class SPDConv(HipModule):
     (``cat([x[..., ::2, ::2], x[..., 1::2, ::2], x[..., ::2, 1::2], x[..., 1::2, 1::2]], 1)``), then Conv(4 * inc, ouc, k=3) -- a
     down-sampling layer that drops no pixel.  The rearrangement is one permutation launch (csrc/spd.hip); the convolution is the
     ordinary 3x3 path on the 4 * inc-channel tensor, its weights in ``state_dict`` order."""
+    concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):
+        return conv_row(cls, row, stride=2)
 
     def __init__(self, inc, ouc, dimension=1):
         super().__init__()
@@ -95,6 +116,11 @@ class DySample(HipModule):
     the checkpoints."""
 
     SUPPORTED = "style='lp', dyscope=False, scale 2 or 4 and in_channels a multiple of 8 * groups"
+    concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:965-967
+        return same_width_row(row, [row.chs[0], *row.args], row.args[0] if row.args else 2)
 
     def __init__(self, in_channels, scale=2, style="lp", groups=4, dyscope=False):
         super().__init__()
@@ -135,6 +161,11 @@ class CARAFE(HipModule):
     the reference's: both Convs are this package's ``Conv``; pixel_shuffle, Upsample and Unfold carry no state."""
 
     SUPPORTED = "k_up=5, scale=2, c a multiple of 8, k_enc 1 or 3"
+    concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:965-967 (DySample's branch); scale 2 is the only one the module takes
+        return same_width_row(row, [row.chs[0], *row.args], 2)
 
     def __init__(self, c, k_enc=3, k_up=5, c_mid=64, scale=2):
         super().__init__()
@@ -167,6 +198,11 @@ class ADown(HipModule):
     ``cv1`` (Conv 3x3 s2) and the second half through a 3x3 s2 max pool and ``cv2`` (Conv 1x1), concatenated.  The average, the
     chunk and the max pool are one launch (csrc/adown.hip); both Convs are this package's ``Conv`` and write the two halves of one
     output buffer.  Attribute names, ``state_dict`` keys and initialisation are the reference's."""
+    concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:840
+        return conv_row(cls, row, stride=2, check=lambda row, c1, c2, a: adown_check(row.layer, c1, c2))
 
     def __init__(self, c1, c2):
         super().__init__()
@@ -204,6 +240,21 @@ class Fusion(HipModule):
     gradient is a dot product over whole maps (csrc/fusion.hip).  Mode 'concat' is the engine's Concat and has no parameter.
     Constructor signature, attribute names (``fusion``, ``fusion_weight``, ``relu``, ``epsilon``) and ``state_dict`` keys are the
     reference's, so its pickles rebuild; the other modes ('weight', 'adaptive', 'SDI') raise."""
+    # (concat_dst stays False although 'bifpn' takes ``out``: that is how the Concat plan was before the attribute, not a decision)
+
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:922-925: the mode is looked up in the YAML dict, so its NAME is a top-level key
+        args, d = row.args, row.yaml
+        if not (args and isinstance(args[0], str) and args[0] in d):
+            raise KeyError(f"{row.layer}: its argument {args[0] if args else None!r} must name a top-level key of the model YAML that "
+                           f"holds the fusion mode (e.g. 'fusion_mode: bifpn')")
+        mode, c1 = d[args[0]], row.chs
+        fusion_check(row.layer, c1, mode)
+        if mode == "bifpn" and len(set(row.down)) != 1:
+            raise NotImplementedError(f"{row.layer}(inc_list={c1}, fusion={mode!r}) reads maps of different sizes (down-sampling "
+                                      f"{row.down}): outside the HIP hot path (supported: fusion 'bifpn' over 2 or 3 inputs of "
+                                      f"one width and map size)")
+        return [c1, mode], (sum(c1) if mode == "concat" else c1[0]), row.down[0]
 
     def __init__(self, inc_list, fusion="bifpn"):
         super().__init__()
@@ -250,6 +301,11 @@ class GSConv(HipModule):
     depthwise 5x5, then the channel shuffle ``cat(x2[:, 0::2], x2[:, 1::2])`` -- one launch that reads x1 and cv2's output where they
     lie (csrc/gsconv.hip, ``Engine.gsconv``).  ``act`` is accepted and ignored, as in the reference: both Convs always use SiLU.
     Attribute names, ``state_dict`` keys and initialisation are the reference's."""
+    concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:828
+        return conv_row(cls, row, stride_arg=True, check=lambda row, c1, c2, a: gsconv_check(row.layer, *a[:7]))
 
     def __init__(self, c1, c2, k=1, s=1, p=None, g=1, d=1, act=True):
         super().__init__()
@@ -288,6 +344,11 @@ class VoVGSCSP(HipModule):
     reference: its parameters and BatchNorm buffers are in ``state_dict()`` and in the parameter count, and nothing ever reads or
     changes them (``unused_modules``: no ConvSpec, no pack, no launch, no gradient, no optimizer update).  ``cv2`` and the last
     bottleneck's sum write the two halves of one buffer that ``cv3`` reads, or stay where they are as the members of a segment table."""
+    repeat_is_arg = concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:828, :874-875; (a[2], when present, is ``shortcut``: n goes in front of it)
+        return conv_row(cls, row, check=lambda row, c1, c2, a: gsconv_check(row.layer, c1, c2, e=a[4] if len(a) > 4 else 0.5))
 
     def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
         super().__init__()

@@ -5,6 +5,7 @@ import torch
 import torch.nn as nn
 
 from ...hip.runtime import HipModule
+from ..rows import conv_row, hidden_width_check
 from .conv import Conv
 
 __all__ = ("DFL", "SPPF", "C2f", "Bottleneck")
@@ -43,6 +44,11 @@ class Bottleneck(HipModule):
 class C2f(HipModule):
     """CSP bottleneck with two convolutions (reference nn/modules/block.py:209-232).  chunk/cat are free: cv1 writes its
     two halves and every Bottleneck its output straight into channel slices of ONE buffer that cv2 then reads."""
+    repeat_is_arg = concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):
+        return conv_row(cls, row, check=lambda row, c1, c2, a: hidden_width_check(row, int(c2 * 0.5), f"its output {c2}"))
 
     def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5):
         super().__init__()
@@ -86,6 +92,11 @@ class C2f(HipModule):
 
 class SPPF(HipModule):
     """Spatial pyramid pooling - fast (reference nn/modules/block.py:151-171)."""
+    concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):
+        return conv_row(cls, row, check=lambda row, c1, c2, a: hidden_width_check(row, c1 // 2, f"its input {c1}"))
 
     def __init__(self, c1, c2, k=5):
         super().__init__()

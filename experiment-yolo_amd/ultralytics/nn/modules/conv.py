@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from ...hip import DY_ACT_NONE, DY_ACT_SILU
 from ...hip.runtime import HipModule
+from ..rows import conv_row
 
 __all__ = ("Conv", "DWConv", "DSConv", "LDConv", "Concat", "autopad")
 # DY_SPLIT_COUT=0: one launch per fused conv whatever its output width (the last 64-wide cout group zero-padded)
@@ -43,6 +44,11 @@ class Conv(HipModule):
     """conv(bias-free) -> BatchNorm2d -> SiLU; args (c1, c2, k, s, p, g, d, act) as reference nn/modules/conv.py:41-59.  g == c1 with a
     supported geometry is a depthwise convolution (``depthwise_check``); any other g != 1 raises."""
     default_act = nn.SiLU()
+    ragged_in = ragged_out = concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):
+        return conv_row(cls, row, stride_arg=True)
 
     def __init__(self, c1, c2, k=1, s=1, p=None, g=1, d=1, act=True):
         super().__init__()
@@ -103,6 +109,12 @@ class Conv(HipModule):
 
 class DWConv(Conv):
     """Depth-wise convolution (reference nn/modules/conv.py:106-111): Conv with g = gcd(c1, c2)."""
+    ragged_out = False
+
+    @classmethod
+    def yaml_row(cls, row):  # the YAML row shows what the constructor would refuse: name the layer
+        return conv_row(cls, row, stride_arg=True, check=lambda row, c1, c2, a: depthwise_check(
+            row.layer, c1, c2, a[2] if len(a) > 2 else 1, a[3] if len(a) > 3 else 1, math.gcd(c1, c2), a[4] if len(a) > 4 else 1))
 
     def __init__(self, c1, c2, k=1, s=1, d=1, act=True):  # ch_in, ch_out, kernel, stride, dilation, activation
         super().__init__(c1, c2, k, s, g=math.gcd(c1, c2), d=d, act=act)
@@ -111,6 +123,11 @@ class DWConv(Conv):
 class DSConv(HipModule):
     """Depthwise separable convolution (reference nn/modules/conv.py:113-122): DWConv(c1, c1, 3) then Conv(c1, c2, 1); k, s, d and act
     are accepted and ignored, exactly as the reference does."""
+    concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):
+        return conv_row(cls, row, check=lambda row, c1, c2, a: depthwise_check(f"layer {row.i} (DSConv.dwconv)", c1, c1, 3, 1, c1))
 
     def __init__(self, c1, c2, k=1, s=1, d=1, act=True):
         super().__init__()
@@ -127,6 +144,10 @@ class DSConv(HipModule):
 class Concat(HipModule):
     """Channel concatenation (reference nn/modules/conv.py:338-348)."""
 
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:905-906
+        return row.args, sum(row.chs), row.down[0]
+
     def __init__(self, dimension=1):
         super().__init__()
         self.d = dimension
@@ -140,6 +161,11 @@ class Concat(HipModule):
 class LDConv(HipModule):
     """Linear deformable convolution (reference nn/modules/conv.py:350-503): offsets from a 3x3 conv, N bilinear samples
     per output pixel, (N,1) column conv -> BN -> SiLU."""
+    concat_dst = True
+
+    @classmethod
+    def yaml_row(cls, row):
+        return conv_row(cls, row, stride_arg=True)
 
     def __init__(self, inc, outc, num_param, stride=1, bias=None):
         super().__init__()

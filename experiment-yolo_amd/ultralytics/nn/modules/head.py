@@ -76,6 +76,11 @@ class Detect(HipModule):
     shape = None
     anchors = torch.empty(0)
     strides = torch.empty(0)
+    ragged_in = True  # (its Conv / nn.Conv2d chains read any width)
+
+    @classmethod
+    def yaml_row(cls, row):  # reference tasks.py:907-911
+        return [*row.args, row.chs], row.nc + 64, row.down[0]
 
     def __init__(self, nc=80, ch=()):
         super().__init__()

@@ -9,7 +9,6 @@ Differences from the reference that are deliberate:
 from __future__ import annotations
 
 import contextlib
-import math
 import re
 from copy import deepcopy
 from pathlib import Path
@@ -21,26 +20,30 @@ import yaml
 from ..hip.engine import Act
 from ..hip.runtime import HipModule, Runtime
 from .extra_modules.attention import SimAM
-from .extra_modules.block import (CARAFE, ADown, Add, DySample, Fusion, GSConv, ScalSeq, SPDConv, VoVGSCSP, Zoom_cat, adown_check, fusion_check,
-                                  gsconv_check)
+from .extra_modules.block import CARAFE, ADown, Add, DySample, Fusion, GSConv, ScalSeq, SPDConv, VoVGSCSP, Zoom_cat
 from .modules import SPPF, C2f, Concat, Conv, Detect, DSConv, DWConv, LDConv
-from .modules.conv import depthwise_check
+from .rows import Row, make_divisible, same_width_row
 
 CFG_MODELS = Path(__file__).resolve().parent.parent / "cfg" / "models"
 
 
-def make_divisible(x, divisor=8):
-    return int(math.ceil(x / divisor) * divisor)
-
-
 class Upsample(HipModule):
     """nn.Upsample(None, 2, 'nearest') of the model YAMLs, on the HIP engine."""
+    concat_dst = True
+    reference_path = "torch.nn.modules.upsampling.Upsample"  # the ``type`` of its layer, as the reference prints it
+
+    @classmethod
+    def yaml_row(cls, row):
+        return same_width_row(row, row.args, int(row.args[1]))
 
     def __init__(self, size=None, scale_factor=None, mode="nearest"):
         super().__init__()
         if size is not None or int(scale_factor) != 2 or mode != "nearest":
             raise NotImplementedError("only nn.Upsample(None, 2, 'nearest') is on the hot path")
         self.size, self.scale_factor, self.mode = size, float(scale_factor), mode
+
+    def out_hw(self, h, w):
+        return 2 * h, 2 * w
 
     def forward_act(self, x, out=None):
         return self.rt.eng.upsample2x(x, out)
@@ -74,14 +77,18 @@ def yaml_model_load(path):
 
 
 def parse_model(d, ch, verbose=True):
-    """YAML dict -> (nn.Sequential, savelist, per-layer down-sampling) for the hot-path module names
-    (reference tasks.py:780-1062, branches :825-864 -- DWConv, DSConv, SPDConv, ADown (:840), GSConv and VoVGSCSP (:828; repeats :874-875) are in that list (:825-843) --, :905-911, :922-925 for Fusion,
-    :965-967 for DySample and CARAFE, :969-970 for SimAM, :1001-1008)."""
+    """YAML dict -> (nn.Sequential, savelist, per-layer output width, per-layer down-sampling) for the hot-path module names
+    (reference tasks.py:780-1062).  What a row means for the class it names -- constructor arguments, output width, down-sampling and
+    the class's own refusals, i.e. the reference's branches :825-1008 -- is that class's ``yaml_row`` (nn/rows.py); what is true of
+    every row stays here."""
     nc, scales = d.get("nc"), d.get("scales")
     depth, width, max_channels = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0), float("inf")
     if scales:
         scale = d.get("scale") or tuple(scales.keys())[0]
         depth, width, max_channels = scales[scale]
+
+    def scaled(c, capped=True):
+        return make_divisible((min(c, max_channels) if capped else c) * width, 8)
     chs, down = [ch], [1.0]
     layers, save = [], []
     for i, (f, n, mname, args) in enumerate(d["backbone"] + d["head"]):
@@ -89,97 +96,31 @@ def parse_model(d, ch, verbose=True):
             raise NotImplementedError(f"module '{mname}' is outside the DEAL-YOLO hot path (supported: {sorted(_MODULES)})")
         m = _MODULES[mname]
         args = [nc if a == "nc" else (None if a == "None" else a) for a in args]
-        n_ = n = max(round(n * depth), 1) if n > 1 else n
+        n = max(round(n * depth), 1) if n > 1 else n
         fl = [f] if isinstance(f, int) else list(f)
         # A width that is not a multiple of 8 (a ``Conv [nc, ...]`` layer: the one width make_divisible does not touch) can only be read
         # by a Conv or by Detect's Conv / nn.Conv2d chains: every other module moves or mixes whole 8-channel granules (hip/engine.py)
-        if i > 0 and m not in (Conv, DWConv, Detect):
+        if i > 0 and not m.ragged_in:
             for j in fl:
                 if chs[j] % 8:
                     raise NotImplementedError(f"layer {i} ({mname}) reads layer {j if j >= 0 else i + j}, which is {chs[j]} channels wide: a width "
                                               f"that is not a multiple of 8 can only feed a Conv or Detect")
-        if m in (LDConv, C2f, SPPF, SPDConv, DWConv, DSConv, ADown, GSConv, VoVGSCSP) and args[0] == nc and nc % 8:
-            raise NotImplementedError(f"layer {i} ({mname}) would be {nc} channels wide: only a Conv can produce a width that is not a multiple of 8")
-        if m in (C2f, SPPF) and i > 0:  # their hidden widths (C2f: the chunk of cv1's output, SPPF: the pooled slices) are granules too
-            c2_ = args[0] if args[0] == nc else make_divisible(min(args[0], max_channels) * width, 8)
-            hidden = int(c2_ * 0.5) if m is C2f else chs[f] // 2
-            if hidden % 8:
-                raise NotImplementedError(f"layer {i} ({mname}) has a hidden width of {hidden} channels ({'its output ' + str(c2_) if m is C2f else 'its input ' + str(chs[f])}"
-                                          f" halved): not a multiple of 8")
-        if m in (Conv, DWConv, DSConv, LDConv, C2f, SPPF, SPDConv, ADown, GSConv, VoVGSCSP):
-            c1, c2 = chs[f], args[0]
-            if c2 != nc:
-                c2 = make_divisible(min(c2, max_channels) * width, 8)
-            args = [c1, c2, *args[1:]]
-            if m is DWConv:  # the YAML row shows what the constructor would refuse: name the layer
-                depthwise_check(f"layer {i} (DWConv)", c1, c2, args[2] if len(args) > 2 else 1, args[3] if len(args) > 3 else 1, math.gcd(c1, c2),
-                                args[4] if len(args) > 4 else 1)
-            elif m is DSConv:
-                depthwise_check(f"layer {i} (DSConv.dwconv)", c1, c1, 3, 1, c1)
-            elif m is ADown:
-                adown_check(f"layer {i} (ADown)", c1, c2)
-            elif m is GSConv:
-                gsconv_check(f"layer {i} (GSConv)", *args[:7])
-            elif m is VoVGSCSP:  # (args[2], when present, is ``shortcut``: n is inserted below)
-                gsconv_check(f"layer {i} (VoVGSCSP)", c1, c2, e=args[4] if len(args) > 4 else 0.5)
-            if m in (C2f, VoVGSCSP):
-                args.insert(2, n)
-                n = 1
-            s = 2 if m in (SPDConv, ADown) else args[3] if (m in (Conv, DWConv, LDConv, GSConv) and len(args) > 3) else 1
-            ds = down[f] * s
-        elif m is Upsample:
-            c2, ds = chs[f], down[f] / int(args[1])
-        elif m is DySample:  # reference tasks.py:965-967
-            c2 = chs[f]
-            args = [c2, *args]
-            ds = down[f] / (args[1] if len(args) > 1 else 2)
-        elif m is CARAFE:  # reference tasks.py:965-967 (the same branch); scale 2 is the only one the module takes
-            c2 = chs[f]
-            args = [c2, *args]
-            ds = down[f] / 2
-        elif m is SimAM:  # reference tasks.py:969-970: ``c2 = ch[f]``, the args passed through (SpatialGroupEnhance shares the branch
-            c2, ds = chs[f], down[f]  # there and is no hot-path name here); a width off the 8-channel granule was refused above
-            args = [float(a) if isinstance(a, str) else a for a in args]  # YAML 1.1 reads ``1e-4`` as a string; the reference evals it (:817)
-        elif m is Concat:
-            c2, ds = sum(chs[x] for x in fl), down[fl[0]]
-        elif m is Zoom_cat:
-            c2, ds = sum(chs[x] for x in fl), down[fl[1]]
-        elif m is Add:
-            c2, ds = chs[fl[-1]], down[fl[-1]]
-        elif m is Fusion:  # reference tasks.py:922-925: the mode is looked up in the YAML dict, so its NAME is a top-level key
-            if not (args and isinstance(args[0], str) and args[0] in d):
-                raise KeyError(f"layer {i} (Fusion): its argument {args[0] if args else None!r} must name a top-level key of the model YAML that "
-                               f"holds the fusion mode (e.g. 'fusion_mode: bifpn')")
-            mode = d[args[0]]
-            c1 = [chs[x] for x in fl]
-            fusion_check(f"layer {i} (Fusion)", c1, mode)
-            if mode == "bifpn" and len({down[x] for x in fl}) != 1:
-                raise NotImplementedError(f"layer {i} (Fusion)(inc_list={c1}, fusion={mode!r}) reads maps of different sizes (down-sampling "
-                                          f"{[down[x] for x in fl]}): outside the HIP hot path (supported: fusion 'bifpn' over 2 or 3 inputs of "
-                                          f"one width and map size)")
-            c2, ds = (sum(c1) if mode == "concat" else chs[fl[0]]), down[fl[0]]
-            args = [c1, mode]
-        elif m is ScalSeq:
-            c1 = [chs[x] for x in fl]
-            c2 = make_divisible(args[0] * width, 8)
-            args, ds = [c1, c2], down[fl[0]]
-        elif m is Detect:
-            args.append([chs[x] for x in fl])
-            c2, ds = sum(args[1]) if False else nc + 64, down[fl[0]]
+        row = Row(i, mname, fl, n, args, nc, [chs[j] for j in fl], [down[j] for j in fl], scaled, d)
+        args, c2, ds = m.yaml_row(row)
+        if m.repeat_is_arg:
+            n = 1
         m_ = nn.Sequential(*(m(*args) for _ in range(n))) if n > 1 else m(*args)
-        t = f"{m.__module__}.{m.__name__}" if m is not Upsample else "torch.nn.modules.upsampling.Upsample"
         m_.np = sum(x.numel() for x in m_.parameters())
-        m_.i, m_.f, m_.type = i, f, t
+        m_.i, m_.f, m_.type = i, f, getattr(m, "reference_path", f"{m.__module__}.{m.__name__}")
         if m is Detect:
-            m_.stride = torch.tensor([down[x] for x in fl], dtype=torch.float32)
+            m_.stride = torch.tensor(row.down, dtype=torch.float32)
         save.extend(x % i for x in fl if x != -1)
         layers.append(m_)
         if i == 0:
             chs, down = [], []
         chs.append(c2)
         down.append(ds)
-        _ = n_
-    return nn.Sequential(*layers), sorted(save)
+    return nn.Sequential(*layers), sorted(save), chs, down
 
 
 def initialize_weights(model):
@@ -230,9 +171,7 @@ class BaseModel(HipModule):
                 fl = [m.i + j if j < 0 else j for j in m.f]
                 if len(set(fl)) != len(fl) or any(j in plan for j in fl):
                     continue
-                ok = all(isinstance(self.model[j], (Conv, DSConv, LDConv, C2f, SPPF, SPDConv, ADown, GSConv, VoVGSCSP, DySample, CARAFE, Upsample, Add, ScalSeq))
-                         for j in fl)
-                if ok:
+                if all(getattr(self.model[j], "concat_dst", False) for j in fl):
                     for pos, j in enumerate(fl):
                         plan[j] = (m.i, pos)
         return plan
@@ -265,12 +204,7 @@ class BaseModel(HipModule):
                 cat_m = self.model[ci]
                 fl = [cat_m.i + j if j < 0 else j for j in cat_m.f]
                 src0 = x[0] if isinstance(x, (list, tuple)) else x
-                if isinstance(m, Upsample):
-                    oh, ow = 2 * src0.H, 2 * src0.W
-                elif hasattr(m, "out_hw"):
-                    oh, ow = m.out_hw(src0.H, src0.W)
-                else:
-                    oh, ow = src0.H, src0.W
+                oh, ow = m.out_hw(src0.H, src0.W) if hasattr(m, "out_hw") else (src0.H, src0.W)
                 if ci not in cats:
                     widths = [self._cout[j] for j in fl]
                     cats[ci] = (eng.new_storage(src0.N, oh, ow, sum(widths)), widths)
@@ -423,10 +357,9 @@ class DetectionModel(BaseModel):
         ch = self.yaml["ch"] = self.yaml.get("ch", ch)
         if nc and nc != self.yaml["nc"]:
             self.yaml["nc"] = nc
-        self.model, self.save = parse_model(deepcopy(self.yaml), ch=ch, verbose=verbose)
+        self.model, self.save, self._cout, _ = parse_model(deepcopy(self.yaml), ch=ch, verbose=verbose)
         self.names = {i: f"{i}" for i in range(self.yaml["nc"])}
         self.inplace = self.yaml.get("inplace", True)
-        self._cout = self._layer_channels(ch)
         m = self.model[-1]
         if isinstance(m, Detect):
             m.inplace = self.inplace
@@ -458,40 +391,6 @@ class DetectionModel(BaseModel):
                 mod.num_batches_tracked.fill_(1)
             if isinstance(mod, ScalSeq):
                 mod.bn.running_mean.copy_(0.1 * mod.conv3d.bias.detach())
-
-    def _layer_channels(self, ch):
-        out = []
-        for m in self.model:
-            if isinstance(m, Conv):
-                out.append(m.conv.out_channels)
-            elif isinstance(m, LDConv):
-                out.append(m.conv[0].out_channels)
-            elif isinstance(m, SPDConv):
-                out.append(m.conv.conv.out_channels)
-            elif isinstance(m, DSConv):
-                out.append(m.pwconv.conv.out_channels)
-            elif isinstance(m, ADown):
-                out.append(2 * m.c)
-            elif isinstance(m, GSConv):
-                out.append(2 * m.cv1.conv.out_channels)
-            elif isinstance(m, VoVGSCSP):
-                out.append(m.cv3.conv.out_channels)
-            elif isinstance(m, (C2f, SPPF)):
-                out.append(m.cv2.conv.out_channels)
-            elif isinstance(m, (Upsample, DySample, CARAFE, SimAM)):
-                out.append(out[m.i + m.f if m.f < 0 else m.f])
-            elif isinstance(m, (Concat, Zoom_cat)):
-                out.append(sum(out[m.i + j if j < 0 else j] for j in m.f))
-            elif isinstance(m, Add):
-                out.append(out[m.i + m.f[-1] if m.f[-1] < 0 else m.f[-1]])
-            elif isinstance(m, Fusion):
-                ws = [out[m.i + j if j < 0 else j] for j in m.f]
-                out.append(sum(ws) if m.fusion == "concat" else ws[0])
-            elif isinstance(m, ScalSeq):
-                out.append(m.conv3d.out_channels)
-            else:
-                out.append(getattr(m, "no", 0))
-        return out
 
     def _apply(self, fn, *a, **k):
         out = super()._apply(fn, *a, **k)
